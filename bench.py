@@ -18,9 +18,20 @@ Rank 0 prints one JSON line with the driver's fields plus
                    its HIP-event-measured average duration, vs 8 TB/s;
                    `traffic` = PMC-measured HBM bytes per launch from
                    profiles/ when that summary exists.
-  cpu_baseline  -- the C restatement of the reference (oracle/, the CPU path
-                   of the reference's algorithms) timed on this host's cores
-                   over a bounded sample.
+  cpu_baseline  -- (--full) the C restatement of the reference (oracle/, the
+                   CPU path of the reference's algorithms) timed on this
+                   host's cores over a bounded sample.
+
+A plain run sets up, warms up, times the steps and prints the line: every
+figure in it comes from the timed steps' own events.  --full adds what takes
+runs of its own: the cpu_baseline, the device-copy rate beside the fq_mul /
+fr_mul roofline, the separately timed g2_prepare of --workload prepared, and
+the separately launched GLV stages and bit-exact chain of --workload wnaf (whose
+roofline prices the comb multiply alone and is therefore null without --full).
+
+--dump-outputs DIR writes, after the timed steps, what the last step computed
+(the device buffers a caller of the timed path receives) as DIR/<name>.npy, see
+dump_outputs().
 """
 import argparse
 import json
@@ -79,8 +90,16 @@ def parse():
                          "(plumbing test of large shapes)")
     ap.add_argument("--workload", choices=["pairing", "prepared", "prepared_shared", "fq_mul", "fr_mul", "wnaf", "decode", "msm", "verify"],
                     default="pairing")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU-work seconds for cpu_baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the cpu_baseline, the device-copy rate of the "
+                         "fq_mul / fr_mul roofline, prepared's g2_prepare, wnaf's separate GLV stages and "
+                         "bit-exact chain (and with them wnaf's roofline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float64, "
+                         "each u64 word as its low and high 32 bits; a seeded row sample of a large output)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0,
+                    help="with --full: target CPU-work seconds for cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the cpu_baseline out")
     ap.add_argument("--decode", action="store_true",
                     help="verify: start from the pairs' compressed encodings and decode them (checked: "
                          "on-curve + subgroup, ec.rs:785-837, 1448-1509) before the multi_pairing")
@@ -89,7 +108,36 @@ def parse():
     ap.add_argument("--cpu-stub", action="store_true",
                     help="launcher test only: gloo ranks on the CPU, the oracle as the per-rank compute "
                          "(tests/test_bench_launcher.py); not a measurement")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000   # all .npy files of one --dump-outputs together stay under 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: arrays = {name: (rows, words) integer ndarray}, the last
+    timed step's results copied back from the device.  Each is written as
+    DIR/<name>.npy in float64, exactly: a u64 word becomes two columns, its low
+    and its high 32 bits (a u8 status stays one column).  An array whose file
+    would pass its share of DUMP_BUDGET_BYTES is cut to a fixed sample of rows
+    (seed 0, ascending), whose indices go to DIR/<name>_rows.npy; the inputs are
+    seeded too, so two builds run with the same arguments write comparable files."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        a = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+        if a.dtype.itemsize == 8:
+            a = a.view(np.uint32)          # little endian: low half, high half per word
+        row_bytes = 8 * a.shape[1] + 8
+        if a.shape[0] * row_bytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], share // row_bytes, replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64))
 
 
 def _free_port():
@@ -538,6 +586,10 @@ def main():
                 if w is not None:
                     w.wait()
                     works[k] = None
+
+        def outputs():
+            # the last step's slot (this rank's own batch)
+            return {"pairing": outs[(nstep[0] - 1) % len(outs)]}
     elif args.workload == "prepared":
         # the north-star's own call shape: Bls12::miller_loop over (G1Affine,
         # G2Prepared) pairs + final_exponentiation, the G2Prepared records (68
@@ -554,13 +606,16 @@ def main():
         out = pdev.empty_records(n, 72, dev)
         scratch = pdev.empty_records(n, 72, dev)
         prep_ms = []
-        for _ in range(3):
+        for _ in range(3 if args.full else 1):
             e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             e[0].record(stream)
             pdev.g2_prepare(q, qp, stream)
             e[1].record(stream)
             torch.cuda.synchronize()
             prep_ms.append(e[0].elapsed_time(e[1]))
+
+        def outputs():
+            return {"pairing": out}
 
         def step(timed):
             if timed:
@@ -591,6 +646,9 @@ def main():
         out = pdev.empty_records(n, 72, dev)
         scratch = pdev.empty_records(n, 72, dev)
 
+        def outputs():
+            return {"pairing": out}
+
         def step(timed):
             if timed:
                 ev[0].record(stream)
@@ -617,6 +675,9 @@ def main():
         scal = torch.from_numpy(s_np.view(np.int64)).to(dev)
         out = pdev.empty_records(n, 18, dev)
         fb_table, fb_ws = pdev.fixed_base_buffers(dev)
+
+        def outputs():
+            return {"points": out}
 
         def step(timed):
             # one Wnaf::base(g, n).scalar(s_i) call: table build overlapped with
@@ -681,6 +742,9 @@ def main():
         st1 = torch.empty(n, dtype=torch.uint8, device=dev)
         st2 = torch.empty(n, dtype=torch.uint8, device=dev)
 
+        def outputs():
+            return {"g1": out1, "g1_status": st1, "g2": out2, "g2_status": st2}
+
         def step(timed):
             if timed:
                 ev[0].record(stream)
@@ -728,6 +792,10 @@ def main():
             total = pdev.empty_records(1, 18, dev)
         torch.cuda.synchronize()
 
+        def outputs():
+            # the sum of every rank's terms on the root, else this rank's sum
+            return {"sum": total if dist_on else msm_out}
+
         def step(timed):
             if timed:
                 ev[0].record(stream)
@@ -772,6 +840,14 @@ def main():
             # checked decodes, then the pairing (A/B)
             split = os.environ.get("PA_VERIFY_SPLIT", "1") != "0"
 
+        def outputs():
+            res = {"product": out, "ok": okb}
+            if args.decode:
+                res.update({"g1_status": st1, "g2_status": st2})
+                if split:
+                    res.update({"g1_in_subgroup": in1, "g2_in_subgroup": in2})
+            return res
+
         def step(timed):
             if timed:
                 ev[0].record(stream)
@@ -809,6 +885,9 @@ def main():
         b = torch.from_numpy(np.ascontiguousarray(b_np).view(np.int64)).to(dev)
         out = pdev.empty_records(n, 4, dev)
 
+        def outputs():
+            return {"product": out}
+
         def step(timed):
             if timed:
                 ev[0].record(stream)
@@ -834,6 +913,10 @@ def main():
             b = torch.from_numpy(b_np.view(np.int64)).to(dev)
             out = pdev.empty_records(n, 6, dev)
             mul = pdev.fq_mul
+
+        def outputs():
+            # one row per product in either layout
+            return {"product": out.t() if args.layout == "soa" else out}
 
         def step(timed):
             if timed:
@@ -871,6 +954,9 @@ def main():
     elapsed = float(t.item())
     ms_per_step = elapsed * 1e3 / args.steps
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in outputs().items()})
+
     if rank == 0:
         if args.workload == "pairing":
             ml = float(np.mean(k_ms["a"]))
@@ -900,8 +986,9 @@ def main():
                                   "G2Prepared materialized in HBM (19 592 B per pair)",
                       "batch_per_gpu": n, "global_batch": n_global,
                       "parallelism": "shard%d+rccl_gather" % ws if dist_on else "single",
-                      "kernel_ms": {"miller_loop_prepared": round(ml, 3), "final_exponentiation": round(fe, 3),
-                                    "untimed: g2_prepare": round(float(np.median(prep_ms)), 3)}}
+                      "kernel_ms": {"miller_loop_prepared": round(ml, 3), "final_exponentiation": round(fe, 3)}}
+            if args.full:
+                config["kernel_ms"]["untimed: g2_prepare"] = round(float(np.median(prep_ms)), 3)
         elif args.workload == "prepared_shared":
             ml = float(np.mean(k_ms["a"]))
             fe = float(np.mean(k_ms["b"]))
@@ -917,18 +1004,24 @@ def main():
                       "kernel_ms": {"miller_loop_shared": round(ml, 3), "final_exponentiation": round(fe, 3)}}
         elif args.workload == "wnaf":
             tot_ms, norm_ms = float(np.mean(k_ms["a"])), float(np.mean(k_ms["b"]))
-            table_ms, mul_ms = comb_parts_ms()
-            x_ms = exact_ms()
-            dom_name, dom_ms, dom_bytes = ("g1_glv_comb_mul", mul_ms, 32 + 144) if mul_ms >= norm_ms else \
-                ("g1_batch_normalize", norm_ms, 144 + 144)
             value = n_global * args.steps / elapsed
             metric, unit = "G1 fixed-base scalar mults + batch_normalization per second at batch 2^18", "points/s"
             config = {"workload": "Wnaf::base(g, 2^18).scalar(s_i) then G1::batch_normalization",
                       "batch_per_gpu": n, "global_batch": n_global,
                       "kernel_ms": {"table+fixed_base_mul (overlapped)": round(tot_ms, 3),
-                                    "batch_normalize": round(norm_ms, 3),
-                                    "separately: glv table": round(table_ms, 3), "separately: glv mul": round(mul_ms, 3),
-                                    "separately: bit-exact wnaf (reference chain, same scalars)": round(x_ms, 3)}}
+                                    "batch_normalize": round(norm_ms, 3)}}
+            # the roofline prices the comb multiply alone, which only the separate
+            # launches of --full time; without them the normalization stands in
+            # below and the line's roofline is null
+            dom_name, dom_ms, dom_bytes = "g1_batch_normalize", norm_ms, 144 + 144
+            if args.full:
+                table_ms, mul_ms = comb_parts_ms()
+                x_ms = exact_ms()
+                if mul_ms >= norm_ms:
+                    dom_name, dom_ms, dom_bytes = "g1_glv_comb_mul", mul_ms, 32 + 144
+                config["kernel_ms"].update({
+                    "separately: glv table": round(table_ms, 3), "separately: glv mul": round(mul_ms, 3),
+                    "separately: bit-exact wnaf (reference chain, same scalars)": round(x_ms, 3)})
         elif args.workload == "decode":
             g2_ms, g1_ms = float(np.mean(k_ms["a"])), float(np.mean(k_ms["b"]))
             dom_name, dom_ms, dom_bytes = ("g2_decode_compressed", g2_ms, 96 + 200 + 1) if g2_ms >= g1_ms else \
@@ -995,7 +1088,7 @@ def main():
         roof = {"kernel": dom_name, "bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                 "bytes_per_unit": dom_bytes, "avg_launch_ms": round(dom_ms, 4)}
-        if args.workload in ("fq_mul", "fr_mul"):
+        if args.workload in ("fq_mul", "fr_mul") and args.full:
             # what a plain device copy of the same byte count reaches on this
             # box (read a,b / write out = 2 reads + 1 write; the copy moves
             # 1 read + 1 write per byte pair), for context next to the spec peak
@@ -1120,8 +1213,10 @@ def main():
             roof = {"kernel": "multi_pairing", "bound": "latency", "achieved": round(dom_ms, 4), "peak": None,
                     "unit": "ms", "frac": None, "traffic": None,
                     "note": "dependent product / linear-combination steps of the quad VM (DESIGN.md section 4, cooperative kernels)"}
+        if args.workload == "wnaf" and not args.full:
+            roof = None
         cpu = None
-        if not args.no_cpu_baseline and ws == 1:
+        if args.full and not args.no_cpu_baseline and ws == 1:
             if args.workload == "pairing":
                 cpu = cpu_baseline_pairing(p_np, q_np, args.cpu_seconds)
             elif args.workload == "prepared":

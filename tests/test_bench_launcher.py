@@ -76,6 +76,36 @@ def test_bench_global_batch_ragged_shards():
     assert line["config"]["global_batch"] == 7 and line["config"]["batch_per_gpu"] == 4
 
 
+def test_dump_outputs_is_exact_seeded_and_bounded(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float64 files that hold every u64
+    word exactly (low and high 32 bits), a status byte as one column, and for
+    an array over its share of the budget the same ascending row sample on
+    every call, the files together under 64 MB"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    big = (np.arange(65536 * 72, dtype=np.int64).reshape(65536, 72) * -0x123456789)   # both halves set
+    small = big[:5, :6].copy()
+    st = (np.arange(37) % 3).astype(np.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small, "status": st})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "big_rows.npy", "small.npy", "status.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 1000 * 1000
+    load = lambda d, f: np.load(tmp_path / d / f)
+    for f in files:
+        assert load("a", f).dtype == np.float64 and np.array_equal(load("a", f), load("b", f))
+
+    def words(x):
+        x = x.astype(np.uint64)
+        return (x[:, 0::2] | (x[:, 1::2] << np.uint64(32))).view(np.int64)
+    rows = load("a", "big_rows.npy").astype(np.int64)
+    assert len(rows) > 1000 and (np.diff(rows) > 0).all() and rows[-1] < len(big)
+    assert np.array_equal(words(load("a", "big.npy")), big[rows])
+    assert np.array_equal(words(load("a", "small.npy")), small)
+    assert np.array_equal(load("a", "status.npy")[:, 0], st)
+
+
 def test_kernel_variant_label_follows_the_default_selection(monkeypatch):
     """bench.kernel_variant_label mirrors capi.hip's default selection (lane groups
     in (768, 4096], the quad VM below, lane pairs, split batches up to 34816 with

@@ -34,26 +34,26 @@ for step in "$@"; do
         unittests) run pytest_units 300 python -u -m pytest tests/test_gen_units.py -m gpu -x -v --timeout 120 --timeout-method thread ;;
         sizetests) run pytest_sizes 600 python -u -m pytest tests/test_bench_sizes.py -m gpu -x -v --timeout 300 --timeout-method thread ;;
         smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) run bench 600 python bench.py ;;
+        bench) run bench 600 python bench.py --full ;;
         benchnc) run bench_nc 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline ;;
         verifybench) run bench_verify 300 python bench.py --workload verify --steps 10 --warmup 2 --no-cpu-baseline ;;
-        fqsoa) run bench_fq_soa 300 python bench.py --workload fq_mul --layout soa --steps 20 --warmup 3 --no-cpu-baseline ;;
+        fqsoa) run bench_fq_soa 300 python bench.py --full --workload fq_mul --layout soa --steps 20 --warmup 3 --no-cpu-baseline ;;
         proffqsoa) run prof_fq_soa 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_fq_soa -o run -- python bench.py --workload fq_mul --layout soa --steps 10 --warmup 2 --no-cpu-baseline ;;
         soatests) run pytest_soa 300 python -u -m pytest tests/test_bench_sizes.py -m gpu -k "soa or fq_mul" -v --timeout 120 --timeout-method thread ;;
         rcclbench) run bench_rccl1 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 5 --warmup 1 --no-cpu-baseline ;;
         benchgen2) run bench_gen2 600 env PA_PAIRING_KERNEL=1 python bench.py --no-cpu-baseline ;;
-        wnafbench) run bench_wnaf 300 python bench.py --workload wnaf --steps 5 --warmup 1 ;;
-        decbench) run bench_decode 300 python bench.py --workload decode --steps 5 --warmup 1 ;;
+        wnafbench) run bench_wnaf 300 python bench.py --full --workload wnaf --steps 5 --warmup 1 ;;
+        decbench) run bench_decode 300 python bench.py --full --workload decode --steps 5 --warmup 1 ;;
         newtests) run pytest_new 600 python -u -m pytest tests/test_fr.py tests/test_msm.py -m gpu -v --timeout 300 --timeout-method thread ;;
-        frbench) run bench_fr 300 python bench.py --workload fr_mul --steps 20 --warmup 3 ;;
+        frbench) run bench_fr 300 python bench.py --full --workload fr_mul --steps 20 --warmup 3 ;;
         msmtests) run pytest_msm 600 python -u -m pytest tests/test_msm.py tests/test_gpu_parity.py -m gpu -x -v --timeout 120 --timeout-method thread ;;
-        msmbench) run bench_msm 400 python bench.py --workload msm --steps 5 --warmup 1 ;;
+        msmbench) run bench_msm 400 python bench.py --full --workload msm --steps 5 --warmup 1 ;;
         profmsm) run prof_msm 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_msm -o run -- python bench.py --workload msm --steps 3 --warmup 1 --no-cpu-baseline ;;
         profwnaf) run prof_wnaf 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_wnaf -o run -- python bench.py --workload wnaf --steps 3 --warmup 1 --no-cpu-baseline ;;
         profdec) run prof_dec 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_dec -o run -- python bench.py --workload decode --steps 3 --warmup 1 --no-cpu-baseline ;;
-        fqbench) run bench_fq 300 python bench.py --workload fq_mul --steps 20 --warmup 3 --no-cpu-baseline ;;
+        fqbench) run bench_fq 300 python bench.py --full --workload fq_mul --steps 20 --warmup 3 --no-cpu-baseline ;;
         prof) run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline ;;
-        frbench_nc) run bench_fr 300 python bench.py --workload fr_mul --steps 20 --warmup 3 --no-cpu-baseline ;;
+        frbench_nc) run bench_fr 300 python bench.py --full --workload fr_mul --steps 20 --warmup 3 --no-cpu-baseline ;;
         proffq) run prof_fq 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_fq -o run -- python bench.py --workload fq_mul --steps 10 --warmup 2 --no-cpu-baseline ;;
         pmc) run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o run -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline &&
              run pmc_write 600 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write -o run -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline ;;
@@ -80,22 +80,22 @@ for step in "$@"; do
                 run dist1_msm_global 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29514 bench.py --workload msm --global-batch 1000003 --steps 3 --warmup 1 --no-cpu-baseline ;;
         profverify) run prof_verify 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_verify -o run -- python bench.py --workload verify --steps 10 --warmup 2 --no-cpu-baseline ;;
         profprep) run prof_prep 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_prep -o run -- python bench.py --workload prepared --steps 3 --warmup 1 --no-cpu-baseline ;;
-        prepbench) run bench_prepared 400 python bench.py --workload prepared --steps 5 --warmup 1 ;;
+        prepbench) run bench_prepared 400 python bench.py --full --workload prepared --steps 5 --warmup 1 ;;
         preptests) run pytest_prep 600 python -u -m pytest tests/test_bench_sizes.py tests/test_gpu_parity.py -m gpu -k "prepare or miller_loop" -x -v --timeout 300 --timeout-method thread ;;
-        verifycpu) run bench_verify_cpu 300 python bench.py --workload verify --steps 10 --warmup 2 ;;
-        allbench) run bench 600 python bench.py &&
-                  run bench_prepared 300 python bench.py --workload prepared --steps 20 --warmup 5 &&
-                  run bench_prepared_shared 300 python bench.py --workload prepared_shared --steps 20 --warmup 5 &&
-                  run bench_verify_cpu 300 python bench.py --workload verify --steps 10 --warmup 2 &&
-                  run bench_verify_decode 300 python bench.py --workload verify --decode --steps 10 --warmup 2 &&
-                  run bench_decode 300 python bench.py --workload decode --steps 5 --warmup 1 &&
-                  run bench_msm 400 python bench.py --workload msm --steps 5 --warmup 1 &&
-                  run bench_wnaf 300 python bench.py --workload wnaf --steps 5 --warmup 1 &&
-                  run bench_fq 300 python bench.py --workload fq_mul --steps 20 --warmup 3 &&
-                  run bench_fr 300 python bench.py --workload fr_mul --steps 20 --warmup 3 ;;
+        verifycpu) run bench_verify_cpu 300 python bench.py --full --workload verify --steps 10 --warmup 2 ;;
+        allbench) run bench 600 python bench.py --full &&
+                  run bench_prepared 300 python bench.py --full --workload prepared --steps 20 --warmup 5 &&
+                  run bench_prepared_shared 300 python bench.py --full --workload prepared_shared --steps 20 --warmup 5 &&
+                  run bench_verify_cpu 300 python bench.py --full --workload verify --steps 10 --warmup 2 &&
+                  run bench_verify_decode 300 python bench.py --full --workload verify --decode --steps 10 --warmup 2 &&
+                  run bench_decode 300 python bench.py --full --workload decode --steps 5 --warmup 1 &&
+                  run bench_msm 400 python bench.py --full --workload msm --steps 5 --warmup 1 &&
+                  run bench_wnaf 300 python bench.py --full --workload wnaf --steps 5 --warmup 1 &&
+                  run bench_fq 300 python bench.py --full --workload fq_mul --steps 20 --warmup 3 &&
+                  run bench_fr 300 python bench.py --full --workload fr_mul --steps 20 --warmup 3 ;;
         sharedtests) run pytest_shared 600 python -u -m pytest tests/test_shared_prepared.py -m gpu -x -v --timeout 300 --timeout-method thread ;;
         sharedbench) run bench_shared 300 python bench.py --workload prepared_shared --steps 10 --warmup 2 --no-cpu-baseline ;;
-        sharedbenchcpu) run bench_shared_cpu 400 python bench.py --workload prepared_shared --steps 10 --warmup 2 ;;
+        sharedbenchcpu) run bench_shared_cpu 400 python bench.py --full --workload prepared_shared --steps 10 --warmup 2 ;;
         profshared) run prof_shared 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_shared -o run -- python bench.py --workload prepared_shared --steps 5 --warmup 1 --no-cpu-baseline ;;
         pmcpair)  # r05: counters of lane-pair vs one-lane kernels and the leaf probe
             P1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"
