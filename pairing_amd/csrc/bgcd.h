@@ -14,7 +14,8 @@
 //     (u, v) <- the same combination divided by 2^30 mod q (one Montgomery
 //     digit), keeping a = u y and b = v y (mod q).
 // 26 x 30 = 780 >= 2 len(q) - 1 = 761 inner steps, enough for b to reach
-// gcd = 1 (Pornin, Theorem 1); then v = y^-1.
+// gcd = 1 (Pornin, Theorem 1); then v = y^-1.  The loop leaves as soon as
+// a == 0: the remaining steps would not change b or v.
 //
 // Plain 32-bit-word C++ with fully unrolled limb loops (no dynamically indexed
 // register arrays), usable from host code for the CPU test
@@ -163,6 +164,16 @@ PA_HD bool inverse(uint32_t* out, const uint32_t* y) {
 #pragma unroll 1
 #endif
     for (int it = 0; it < kOuter; it++) {
+        // a == 0: every further step has f0 = 1, g0 = 0, f1 = 0, g1 = 2^30 and
+        // leaves b and v (canonical, v 2^30 has Montgomery digit 0) unchanged;
+        // only u, which nothing reads, would move.  Random inputs get here after
+        // 17..20 of the 26 steps, nearly all after 18 or 19 (kOuter stays the
+        // bound); on the device a wave stays in the loop until its last lane
+        // is done.
+        uint32_t az = a[0];
+#pragma unroll
+        for (int i = 1; i < 12; i++) az |= a[i];
+        if (az == 0) break;
         int n = bitlen(a);
         const int nb = bitlen(b);
         n = n > nb ? n : nb;

@@ -200,8 +200,14 @@ def write_work_json(outdir):
         # lane pairs: the DSL counts and the emitter's estimate are per lane;
         # a pairing is two lanes' work
         lanes = prog.lanes
+        # the binary GCD's loop leaves when the wave's last lane has converged: its
+        # rounds are weighted by dsl.BINV_TYPICAL, the 28-round bound is the worst case
         out[name] = {"limb_macs": lanes * macs(st.counts), "ops": st.counts,
                      "instructions": round(lanes * em.dyn_instr), "lanes_per_pairing": lanes}
+        if em.dyn_binv_round:
+            out[name]["instructions_worst_case"] = round(lanes * (
+                em.dyn_instr + (dsl.BINV_OUTER - dsl.BINV_TYPICAL) * em.dyn_binv_round))
+            out[name]["binv_rounds"] = {"typical": dsl.BINV_TYPICAL, "worst_case": dsl.BINV_OUTER}
     with open(os.path.join(outdir, "pa_gen_work.json"), "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
 

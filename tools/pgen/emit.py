@@ -27,7 +27,7 @@ for constants, or label strings; see render.py / sim.py.
 import os
 
 import gen_fl
-from dsl import Loop, If, Op, SUBC, NL, MASK, QL, QINV28, KQ, Q, BINV_OUTER, BINV_PAD, BINV_C
+from dsl import Loop, If, Op, SUBC, NL, MASK, QL, QINV28, KQ, Q, BINV_OUTER, BINV_TYPICAL, BINV_PAD, BINV_C
 
 A_BASE, S_BASE = 256, 512
 VCC = S_BASE + 106
@@ -131,6 +131,8 @@ class Emitter:
         self.mstore = {}                    # M slot -> vm count right after its last (tracked) store
         self.debug = False
         self.weight = 1
+        self.binv_weight = 0         # the enclosing loops' weight inside a binv outer round, else 0
+        self.dyn_binv_round = 0
         self.ensuring = None
         self.pending = {}            # V slot -> ("L" | "M", issue count after its last load)
         self.split_pending = {}      # V slot -> True: raw record words, split when they land
@@ -174,6 +176,7 @@ class Emitter:
     def i(self, *t):
         self.code.append(t)
         self.dyn_instr = getattr(self, "dyn_instr", 0) + self.weight   # loop-weighted estimate
+        self.dyn_binv_round += self.binv_weight   # instructions of one binv outer round, loop-weighted
         m = t[0]
         if m in self.VMEM:
             self.vm_issued += 1
@@ -748,7 +751,12 @@ class Emitter:
         Registers: a, b, u, w = four scratch V slots; work area v0..v15
         (v16 = the lane offset, v17 are kept); s[32:33] s[34:35] s[38:39] VCC
         masks; the outer loop counter at S_CNT + depth.  Every VALU read of an
-        SGPR a VALU wrote comes at least two instructions after the write."""
+        SGPR a VALU wrote comes at least two instructions after the write.
+
+        The counted loop (BINV_OUTER trips, the worst-case bound) also ends
+        after the first round that leaves a = 0 in every active lane of the
+        wave: from then on a round changes neither b nor w (dsl.binv_core_early).
+        The instruction estimate weights a round by BINV_TYPICAL."""
         a, b, u, w = (self.vbase(k) for k in scratch)
         MK = K(MASK)
         # y = x mod q, canonical, into a
@@ -766,11 +774,12 @@ class Emitter:
             self.i("v_mov_b32", u + i, K(1 if i == 0 else 0))
             self.i("v_mov_b32", w + i, K(0))
         cnt = S(S_CNT + self.depth)
-        top = self.label()
+        top, done = self.label(), self.label()
         self.i("s_mov_b32", cnt, K(BINV_OUTER - 1))
         self.i("label", top)
         w0 = self.weight
-        self.weight = w0 * BINV_OUTER
+        self.weight = w0 * BINV_TYPICAL
+        self.binv_weight = w0
         # -- n = max(len(a | b), 58): top nonzero limb (index v13, value v12),
         #    limbs 2..13 (below limb 2 the max with 58 decides anyway)
         masks = (S(32), S(34), S(38))
@@ -823,33 +832,43 @@ class Emitter:
             self.i("v_and_b32", 4, K((1 << 30) - 1), 4)
             self.i("v_lshl_or_b32", dst, 4, K(28), src)
             self.i("v_lshrrev_b32", dst + 1, K(4), 4)
-        # -- 28 inner steps: f0 v6, g0 v7, f1 v8, g1 v9
-        for r, v in ((6, 1), (7, 0), (8, 0), (9, 1)):
-            self.i("v_mov_b32", r, K(v))
-        for _ in range(28):
-            self.i("v_and_b32", 0, K(1), 10)
-            self.i("v_cmp_lt_u64_e64", S(38), 10, 12)          # lt
-            self.i("v_cmp_ne_u32_e64", S(34), K(0), 0)          # odd
-            self.i("s_and_b64", VCC, S(34), S(38))              # swap = odd & lt
-            self.i("v_cndmask_b32_e64", 0, 10, 12, VCC)  # XA = swap ? xb : xa
-            self.i("v_cndmask_b32_e64", 1, 11, 13, VCC)
-            self.i("v_cndmask_b32_e64", 12, 12, 10, VCC)  # xb' = swap ? xa : xb
-            self.i("v_cndmask_b32_e64", 13, 13, 11, VCC)
-            self.i("v_cndmask_b32_e64", 4, 6, 8, VCC)  # FA = swap ? f1 : f0
-            self.i("v_cndmask_b32_e64", 8, 8, 6, VCC)  # FB
-            self.i("v_cndmask_b32_e64", 5, 7, 9, VCC)  # GA
-            self.i("v_cndmask_b32_e64", 9, 9, 7, VCC)  # GB
-            self.i("v_sub_co_u32", 2, 0, 12)                    # XA - XB (borrow in VCC)
-            self.i("v_sub_u32", 14, 4, 8)
-            self.i("v_sub_u32", 15, 5, 9)
-            self.i("v_subb_co_u32", 3, 1, 13)
-            self.i("v_cndmask_b32_e64", 6, 4, 14, S(34))        # f0' = odd ? FA - FB : FA
-            self.i("v_cndmask_b32_e64", 7, 5, 15, S(34))
-            self.i("v_lshlrev_b32", 8, K(1), 8)                 # f1' = 2 FB
-            self.i("v_lshlrev_b32", 9, K(1), 9)
-            self.i("v_cndmask_b32_e64", 10, 0, 2, S(34))        # xa' = (odd ? XA - XB : XA) / 2
-            self.i("v_cndmask_b32_e64", 11, 1, 3, S(34))
-            self.i("v_lshrrev_b64", 10, K(1), 10)
+        # -- 28 inner steps as two halves of 14 with the factors packed: within a
+        #    half |f| + |g| <= 2^14, so a row (f, g) is one register of two signed
+        #    16-bit halves (f low, g high); half h keeps row 0 in v6 + h, row 1 in v8 + h
+        for h in range(2):
+            p0, p1 = 6 + h, 8 + h
+            self.i("v_mov_b32", p0, K(1))                       # (1, 0)
+            self.i("v_mov_b32", p1, K(1 << 16))                 # (0, 1)
+            for _ in range(14):
+                self.i("v_and_b32", 0, K(1), 10)
+                self.i("v_cmp_lt_u64_e64", S(38), 10, 12)          # lt
+                self.i("v_cmp_ne_u32_e64", S(34), K(0), 0)          # odd
+                self.i("s_and_b64", VCC, S(34), S(38))              # swap = odd & lt
+                self.i("v_cndmask_b32_e64", 0, 10, 12, VCC)  # XA = swap ? xb : xa
+                self.i("v_cndmask_b32_e64", 1, 11, 13, VCC)
+                self.i("v_cndmask_b32_e64", 12, 12, 10, VCC)  # xb' = swap ? xa : xb
+                self.i("v_cndmask_b32_e64", 13, 13, 11, VCC)
+                self.i("v_cndmask_b32_e64", 4, p0, p1, VCC)  # RA = swap ? row 1 : row 0
+                self.i("v_cndmask_b32_e64", p1, p1, p0, VCC)  # RB
+                self.i("v_sub_co_u32", 2, 0, 12)                    # XA - XB (borrow in VCC)
+                self.i("v_pk_sub_i16", 14, 4, p1)                   # RA - RB, both halves
+                self.i("v_pk_add_u16", p1, p1, p1)                  # row 1' = 2 RB
+                self.i("v_subb_co_u32", 3, 1, 13)
+                self.i("v_cndmask_b32_e64", p0, 4, 14, S(34))       # row 0' = odd ? RA - RB : RA
+                self.i("v_cndmask_b32_e64", 10, 0, 2, S(34))        # xa' = (odd ? XA - XB : XA) / 2
+                self.i("v_cndmask_b32_e64", 11, 1, 3, S(34))
+                self.i("v_lshrrev_b64", 10, K(1), 10)
+        # -- the round's factors = (second half's matrix) x (first half's), as 32-bit
+        #    values: f0 v6, g0 v7, f1 v8, g1 v9 (every entry of a half is 24-bit signed)
+        for src, lo, hi in ((6, 0, 1), (8, 2, 3), (7, 4, 5), (9, 10, 11)):
+            self.i("v_bfe_i32", lo, src, K(0), K(16))
+            self.i("v_ashrrev_i32", hi, K(16), src)
+        for dst, x, y in ((6, 4, 5), (8, 10, 11)):
+            # (x, y) = a row of the second half: dst = x f0' + y f1', dst + 1 = x g0' + y g1'
+            self.i("v_mul_i32_i24", dst, x, 0)
+            self.i("v_mul_i32_i24", dst + 1, x, 1)
+            self.i("v_mad_i32_i24", dst, y, 2, dst)
+            self.i("v_mad_i32_i24", dst + 1, y, 3, dst + 1)
         # -- (a, b) <- ((a f0 + b g0), (a f1 + b g1)) / 2^28, in place (column i -> limb i - 1)
         self.comb_columns(((a, 6, b, 7, None), (b, 9, a, 8, None)))
         # -- negative results: negate the limbs and the factor row
@@ -865,12 +884,26 @@ class Emitter:
         for r, mreg in ((6, 10), (7, 10), (8, 11), (9, 11)):
             self.i("v_xor_b32", r, r, mreg)
             self.i("v_sub_u32", r, r, mreg)
+        # -- s[32:33] = the lanes with a != 0 (an inactive lane's bit is 0); read by
+        #    SALU after the (u, w) update, which leaves v12 and s[32:33] alone
+        self.i("v_or3_b32", 12, a, a + 1, a + 2)
+        for i in range(3, NL, 2):
+            if i + 1 < NL:
+                self.i("v_or3_b32", 12, 12, a + i, a + i + 1)
+            else:
+                self.i("v_or_b32", 12, 12, a + i)
+        self.i("v_cmp_ne_u32_e64", S(32), K(0), 12)
         # -- (u, w) <- ((u f0 + w g0), (u f1 + w g1)) / 2^28 mod q (one Montgomery digit each)
         self.comb_columns(((u, 6, w, 7, 4), (w, 9, u, 8, 5)))
-        self.weight = w0
+        # -- a = 0 in the whole wave: the remaining rounds would change nothing
+        self.i("s_cmp_eq_u64", S(32), K(0))
+        self.i("long_cbranch_scc1", done)
         self.i("s_sub_u32", cnt, cnt, K(1))
         self.i("s_cmp_ge_i32", cnt, K(0))
         self.i("long_cbranch_scc1", top)
+        self.weight = w0
+        self.binv_weight = 0
+        self.i("label", done)
         # -- w + 32 q >= 0, normalized; times R'^3 (one Montgomery product)
         pad = gen_fl.limbs(BINV_PAD * Q)
         for i in range(NL):

@@ -14,6 +14,11 @@ def sx32(x):
     return x - (1 << 32) if x >> 31 else x
 
 
+def sx24(x):
+    x &= 0xffffff
+    return x - (1 << 24) if x >> 23 else x
+
+
 def sx64(x):
     x &= M64
     return x - (1 << 64) if x >> 63 else x
@@ -43,6 +48,7 @@ class Sim:
         self.labels = {t[1]: i for i, t in enumerate(code) if t[0] == "label"}
         self.count = 0
         self.hist = {}
+        self.taken = {}          # label -> times a branch to it was taken
         self.trace = None
         self.ws = 0              # wait-state clock: +1 per instruction, +N+1 per s_nop N
         self.sgpr_vwrite = {}    # SGPR number -> wait-state clock of its last VALU write
@@ -146,6 +152,13 @@ class Sim:
         m = (m & ~(1 << b)) | (int(bool(bit)) << b)
         self.s[n], self.s[n + 1] = m & M32, m >> 32
 
+    def clear_cmp_mask(self, t):
+        """a VALU compare writes all 64 bits of its mask, 0 for the lanes EXEC
+        masks off -- here every lane that is not simulated; the wave-uniform
+        exit of the binary GCD (emit.emit_binv) compares such a mask with 0"""
+        n = (t[1] - 512) if t[0].endswith("_e64") else 106
+        self.s[n] = self.s[n + 1] = 0
+
     def mask_bit(self, sreg):
         n = sreg - 512
         return ((self.s[n] | (self.s[n + 1] << 32)) >> (self.lane % 64)) & 1
@@ -231,6 +244,8 @@ class Sim:
                         self.vf[ln][t[1]] = val[ln]
                     nxt = None
                 else:
+                    if m.startswith("v_cmp"):
+                        self.clear_cmp_mask(t)
                     for ln in self.lanes:
                         self.lane, self.v, self.a = ln, self.vf[ln], self.af[ln]
                         nxt = self.step(t)
@@ -238,6 +253,8 @@ class Sim:
                 nxt = self.step(t)
             if nxt == "end":
                 return
+            if nxt is not None:
+                self.taken[nxt] = self.taken.get(nxt, 0) + 1
             pc = self.labels[nxt] if nxt is not None else pc + 1
 
     LOFF = 16     # v16 = tid * 8 (emit.LOFF)
@@ -269,6 +286,8 @@ class Sim:
             if m.startswith("global_"):
                 self.seq["vm"] += 1
             if m.startswith("v_") or m.startswith("global_"):
+                if m.startswith("v_cmp"):
+                    self.clear_cmp_mask(t)
                 for ln in range(64):
                     self.lane, (self.v, self.a) = ln, files[ln]
                     self.step(t)
@@ -332,6 +351,19 @@ class Sim:
         elif m == "v_cndmask_b32_e64":
             msk = rd64(a[3])
             wr(a[0], rd(a[2]) if (msk >> (self.lane % 64)) & 1 else rd(a[1]))
+        elif m in ("v_pk_sub_i16", "v_pk_add_u16"):
+            # two independent 16-bit lanes, wrap-around (no clamp)
+            x, y = rd(a[1]), rd(a[2])
+            sg = -1 if m == "v_pk_sub_i16" else 1
+            wr(a[0], ((x + sg * y) & 0xffff) | ((((x >> 16) + sg * (y >> 16)) & 0xffff) << 16))
+        elif m == "v_bfe_i32":
+            off, wd = rd(a[2]) & 31, rd(a[3]) & 31
+            x = (rd(a[1]) >> off) & ((1 << wd) - 1) if wd else 0
+            wr(a[0], x - (1 << wd) if wd and x >> (wd - 1) else x)
+        elif m == "v_mul_i32_i24":
+            wr(a[0], sx24(rd(a[1])) * sx24(rd(a[2])))
+        elif m == "v_mad_i32_i24":
+            wr(a[0], sx24(rd(a[1])) * sx24(rd(a[2])) + sx32(rd(a[3])))
         elif m == "v_mul_u32_u24":
             wr(a[0], (rd(a[1]) & 0xffffff) * (rd(a[2]) & 0xffffff))
         elif m == "v_mov_b32" or m == "v_accvgpr_write_b32" or m == "v_accvgpr_read_b32":
@@ -509,11 +541,17 @@ class Sim:
         return None
 
 
-def run_lane(code, args, buffers, lane=0, max_steps=10 ** 9, trace=None, pair=False, lds=None):
+def run_lane(code, args, buffers, lane=0, max_steps=10 ** 9, trace=None, pair=False, lds=None, lanes=None):
     """args: 5 u64 kernel arguments; buffers: {base_address: list of u64};
-    pair: simulate lanes (lane & ~1, lane | 1) together; lds: {byte address:
-    u32} the wave's other lanes write (a table the whole wave stages)"""
-    sm = Sim(code, lane, [lane & ~1, lane | 1] if pair else None)
+    pair: simulate lanes (lane & ~1, lane | 1) together; lanes: the lanes of
+    one wave to simulate together (e.g. all 64: wave-uniform branches see every
+    lane's mask bit); lds: {byte address: u32} the wave's other lanes write (a
+    table the whole wave stages)"""
+    if lanes is not None:
+        lanes = list(lanes)
+        lane = lanes[0]
+        assert len({ln // 64 for ln in lanes}) == 1
+    sm = Sim(code, lane, lanes or ([lane & ~1, lane | 1] if pair else None))
     sm.lds.update(lds or {})
     sm.trace = iter(trace) if trace is not None else None
     for base, words in buffers.items():
