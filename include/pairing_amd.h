@@ -353,6 +353,38 @@ int pa_g2_multiexp(const pa_g2_affine *bases, const pa_fr_repr *s, size_t n, pa_
 /* device workspace bytes for pa_g{1,2}_multiexp_device (group 1 or 2) */
 size_t pa_multiexp_workspace_bytes(int group, size_t n);
 
+/* ---- G1 multiexp over prepared bases ----
+ * A prover's bases are its proving key: fixed across calls.  pa_g1_msm_bases
+ * holds them on one device in the form the bucket accumulation gathers
+ * (converted once, not per call) together with one flag: whether every base
+ * passed the G1 membership test phi(P) == -[x^2] P at preparation (infinity
+ * passes).  With the flag set, a multiexp splits each scalar s = q x^2 + rem
+ * (integers, any 256-bit s) and sums rem P_i + q (-phi(P_i)) over half as many
+ * windows; with it clear, the same 257-bit pipeline as pa_g1_multiexp runs over
+ * the prepared rows and phi is never used.  Either way the result is equal as
+ * a point (PartialEq, ec.rs:45-85) to the reference's sum of CurveAffine::mul
+ * terms, for every 256-bit FrRepr (values >= r included).  Bases off the curve
+ * are unspecified, as for pa_g1_multiexp.
+ * Preparation runs once and synchronizes the stream; n < 2^30, n = 0 allowed.
+ * The object is tied to the device it was prepared on (the current device, or
+ * the stream's), may be used from any host thread, and lives until
+ * pa_g1_msm_bases_free (NULL is a no-op); work that reads it must have
+ * completed before it is freed. */
+typedef struct pa_g1_msm_bases pa_g1_msm_bases;
+int pa_g1_msm_bases_prepare(const pa_g1_affine *host_bases, size_t n, pa_g1_msm_bases **out);
+int pa_g1_msm_bases_prepare_device(const pa_g1_affine *dev_bases, size_t n, void *stream, pa_g1_msm_bases **out);
+size_t pa_g1_msm_bases_len(const pa_g1_msm_bases *bases);
+int pa_g1_msm_bases_in_subgroup(const pa_g1_msm_bases *bases);   /* 1 or 0 */
+int pa_g1_msm_bases_free(pa_g1_msm_bases *bases);
+/* *out = sum_{i < m} s[i] * P_i over the first m <= len prepared bases; m = 0
+ * gives the zero point.  Errors (m > len, a workspace smaller than
+ * pa_g1_multiexp_prepared_workspace_bytes(bases, m), a stream on another
+ * device than the object's) return a code before anything is launched. */
+size_t pa_g1_multiexp_prepared_workspace_bytes(const pa_g1_msm_bases *bases, size_t m);
+int pa_g1_multiexp_prepared_device(const pa_g1_msm_bases *bases, const pa_fr_repr *dev_scalars, size_t m,
+                                   pa_g1 *dev_out, void *workspace, size_t workspace_bytes, void *stream);
+int pa_g1_multiexp_prepared(const pa_g1_msm_bases *bases, const pa_fr_repr *host_scalars, size_t m, pa_g1 *out);
+
 /* ---- scalar field Fr (src/bls12_381/fr.rs; SURVEY.md §8 f, rank 4) ----
  * pa_fr = 4 x u64 LE limbs, Montgomery form with R = 2^256, < r: the
  * reference's `Fr` in memory.  Every result is canonical, so it equals the

@@ -578,6 +578,42 @@ PA_AFFINE_DEFS(G1Affine, G1, 1)
 PA_AFFINE_DEFS(G2Affine, G2, 2)
 #undef PA_AFFINE_DEFS
 
+// G1 multiexp bases prepared once (pa_g1_msm_bases): the membership check and
+// the conversion pa_g1_multiexp repeats per call, kept on the current device.
+// Move-only; the destructor frees the device memory.
+class G1MsmBases {
+public:
+    explicit G1MsmBases(const std::vector<G1Affine>& bases) {
+        check(pa_g1_msm_bases_prepare(bases.empty() ? nullptr : &bases[0].v, bases.size(), &h_), "G1MsmBases");
+    }
+    G1MsmBases(const G1MsmBases&) = delete;
+    G1MsmBases& operator=(const G1MsmBases&) = delete;
+    G1MsmBases(G1MsmBases&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    G1MsmBases& operator=(G1MsmBases&& o) noexcept {
+        if (this != &o) {
+            (void)pa_g1_msm_bases_free(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~G1MsmBases() { (void)pa_g1_msm_bases_free(h_); }
+
+    size_t size() const { return pa_g1_msm_bases_len(h_); }
+    bool in_subgroup() const { return pa_g1_msm_bases_in_subgroup(h_) != 0; }
+    const pa_g1_msm_bases* get() const { return h_; }
+    // sum_i s_i * bases_i over the first s.size() <= size() bases: the same
+    // point as G1::multiexp over them
+    G1 multiexp(const std::vector<FrRepr>& s) const {
+        G1 r;
+        check(pa_g1_multiexp_prepared(h_, s.empty() ? nullptr : &s[0].v, s.size(), &r.v), "G1MsmBases::multiexp");
+        return r;
+    }
+
+private:
+    pa_g1_msm_bases* h_ = nullptr;
+};
+
 using G1Uncompressed = Encoded<G1Affine, 1, false>;
 using G1Compressed = Encoded<G1Affine, 1, true>;
 using G2Uncompressed = Encoded<G2Affine, 2, false>;

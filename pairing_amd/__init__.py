@@ -16,7 +16,7 @@ Device-resident entry points for torch tensors live in `pairing_amd.device`.
 """
 import numpy as np
 
-from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, PairingError, _lib,
+from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, G1MsmBases, PairingError, _lib,
                       as_rows, call, device_count, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
 
 __all__ = [
@@ -33,6 +33,7 @@ __all__ = [
     "fr_mul", "fr_square", "fr_add", "fr_sub", "fr_double", "fr_negate", "fr_inverse",
     "fr_from_repr", "fr_into_repr", "fr_pow", "fr_legendre", "fr_sqrt",
     "g1_affine_mul", "g2_affine_mul", "g1_mul_assign", "g2_mul_assign", "g1_multiexp", "g2_multiexp",
+    "G1MsmBases", "g1_msm_prepare", "g1_multiexp_prepared",
     "g1_eq", "g2_eq", "g1_double", "g2_double", "g1_add", "g2_add", "g1_add_mixed", "g2_add_mixed", "g1_negate", "g2_negate",
     "g1_sub", "g2_sub", "g1_into_affine", "g2_into_affine", "g1_into_projective", "g2_into_projective",
     "g2_batch_normalization", "g2_wnaf_fixed_base",
@@ -577,6 +578,30 @@ def g1_multiexp(bases, scalars):
 
 def g2_multiexp(bases, scalars):
     return _multiexp("pa_g2_multiexp", bases, scalars, W_G2A, W_G2)
+
+
+def g1_msm_prepare(bases):
+    """Prepare G1 affine bases ((n, 13) rows) for repeated multiexps: checked for G1
+    membership and converted once, kept on the current device.  Returns a G1MsmBases
+    (len, in_subgroup, close()); free it with close() or let it be collected."""
+    import ctypes
+    b = as_rows(bases, W_G1A, "bases") if len(bases) else np.zeros((0, W_G1A), np.uint64)
+    h = ctypes.c_void_p(0)
+    call("pa_g1_msm_bases_prepare", ptr(b), b.shape[0], ctypes.byref(h))
+    return G1MsmBases._adopt(h)
+
+
+def g1_multiexp_prepared(prepared, scalars):
+    """sum_i s_i * P_i over the first len(scalars) prepared bases: one Jacobian row, the
+    same point as g1_multiexp over those bases (any 256-bit FrRepr)."""
+    if not isinstance(prepared, G1MsmBases):
+        raise ValueError("prepared must come from g1_msm_prepare")
+    prepared.handle()   # a closed object is rejected first
+    s = as_rows(scalars, 4, "scalars") if len(scalars) else np.zeros((0, 4), np.uint64)
+    h = prepared.check_terms(s.shape[0])
+    out = np.zeros((1, W_G1), np.uint64)
+    call("pa_g1_multiexp_prepared", h, ptr(s), s.shape[0], ptr(out))
+    return out
 
 
 # ---- CurveProjective / CurveAffine surface for G1 and G2 (ec.rs:1-621) ----

@@ -148,6 +148,14 @@ _SIGS = {
     "pa_g2_multiexp": [_P, _P, _N, _P],
     "pa_g1_multiexp_device": [_P, _P, _N, _P, _P, _N, _P],
     "pa_g2_multiexp_device": [_P, _P, _N, _P, _P, _N, _P],
+    "pa_g1_msm_bases_prepare": [_P, _N, ctypes.POINTER(_P)],
+    "pa_g1_msm_bases_prepare_device": [_P, _N, _P, ctypes.POINTER(_P)],
+    "pa_g1_msm_bases_len": [_P],                      # returns size_t (below)
+    "pa_g1_msm_bases_in_subgroup": [_P],
+    "pa_g1_msm_bases_free": [_P],
+    "pa_g1_multiexp_prepared_workspace_bytes": [_P, _N],   # returns size_t (below)
+    "pa_g1_multiexp_prepared_device": [_P, _P, _N, _P, _P, _N, _P],
+    "pa_g1_multiexp_prepared": [_P, _P, _N, _P],
 }
 for _g in (1, 2):
     for _op in ("double", "negate", "into_affine", "into_projective"):
@@ -194,6 +202,8 @@ _lib.pa_multiexp_workspace_bytes.argtypes = [ctypes.c_int, _N]
 _lib.pa_multiexp_workspace_bytes.restype = ctypes.c_size_t
 _lib.pa_wnaf_exact_workspace_bytes.argtypes = [ctypes.c_int, _N, ctypes.c_int, ctypes.c_int]
 _lib.pa_wnaf_exact_workspace_bytes.restype = ctypes.c_size_t
+_lib.pa_g1_msm_bases_len.restype = ctypes.c_size_t
+_lib.pa_g1_multiexp_prepared_workspace_bytes.restype = ctypes.c_size_t
 
 
 def version():
@@ -248,3 +258,59 @@ def as_rows(a, width, name="array"):
     if a.ndim != 2 or a.shape[1] != width:
         raise ValueError("%s must have shape (n, %d), got %s" % (name, width, a.shape))
     return a
+
+
+class G1MsmBases:
+    """A pa_g1_msm_bases handle: G1 multiexp bases prepared once on one device
+    (include/pairing_amd.h).  `len` and `in_subgroup` are read at creation;
+    close() frees the device memory, is idempotent and also runs when the
+    object is collected.  Any use after close() raises ValueError before a
+    native call.  owns=False wraps a handle someone else frees."""
+
+    def __init__(self, handle, length, in_subgroup, owns=True):
+        self._handle = handle
+        self._owns = owns
+        self.len = int(length)
+        self.in_subgroup = bool(in_subgroup)
+
+    @classmethod
+    def _adopt(cls, handle):
+        """take ownership of a handle a prepare call just returned"""
+        h = ctypes.c_void_p(handle.value)
+        return cls(h, _lib.pa_g1_msm_bases_len(h), _lib.pa_g1_msm_bases_in_subgroup(h))
+
+    def __len__(self):
+        return self.len
+
+    @property
+    def closed(self):
+        return self._handle is None
+
+    def handle(self):
+        if self._handle is None:
+            raise ValueError("prepared multiexp bases used after close()")
+        return self._handle
+
+    def check_terms(self, m):
+        """the handle, after checking that a multiexp over m terms fits"""
+        h = self.handle()
+        if m > self.len:
+            raise ValueError("%d scalars for %d prepared bases" % (m, self.len))
+        return h
+
+    def close(self):
+        h, self._handle = self._handle, None
+        if h is not None and self._owns:
+            call("pa_g1_msm_bases_free", h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: the library may be gone
+            pass

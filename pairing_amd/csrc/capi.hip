@@ -1478,6 +1478,125 @@ int pa_g2_multiexp_device(const pa_g2_affine* bases, const pa_fr_repr* scalars, 
     return PA_OK;
 }
 
+// ---- G1 MSM over prepared bases (kernels_msm.hip) ----
+// The object owns the 2n lazy rows on one device and remembers whether every
+// base passed the G1 membership test: the host picks the GLV pipeline (flag 1)
+// or the 257-bit one over the same rows (flag 0) from it.
+struct pa_g1_msm_bases {
+    int dev = 0;
+    size_t n = 0;
+    int in_subgroup = 0;
+    uint32_t* rows = nullptr;
+};
+
+namespace {
+// the current device switched to `dev` for a scope (allocations belong to the current device)
+struct DeviceScope {
+    int prev = -1;
+    bool switched = false;
+    hipError_t enter(int dev) {
+        hipError_t e = hipGetDevice(&prev);
+        if (e != hipSuccess || prev == dev) return e;
+        if ((e = hipSetDevice(dev)) == hipSuccess) switched = true;
+        return e;
+    }
+    ~DeviceScope() {
+        if (switched) (void)hipSetDevice(prev);
+    }
+};
+}  // namespace
+
+int pa_g1_msm_bases_prepare_device(const pa_g1_affine* bases, size_t n, void* stream, pa_g1_msm_bases** out) {
+    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    *out = nullptr;
+    if (n && !bases) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n >= pa::kMsmPreparedMax) return fail(PA_ERR_INVALID_ARGUMENT, "prepared multiexp bases support n < 2^30");
+    hipStream_t s = (hipStream_t)stream;
+    int dev = 0;
+    PA_TRY(hipStreamGetDevice(s, &dev), "stream device");
+    DeviceScope scope;
+    PA_TRY(scope.enter(dev), "set device");
+    pa_g1_msm_bases* b = new pa_g1_msm_bases;
+    b->dev = dev;
+    b->n = n;
+    b->in_subgroup = 1;
+    if (n == 0) {
+        *out = b;
+        return PA_OK;
+    }
+    // scratch: the per-base membership flags, then the count of failed ones
+    const size_t bad_off = (n + 255) & ~(size_t)255;
+    uint8_t* scratch = nullptr;
+    uint32_t bad = 0;
+    hipError_t e = hipMalloc((void**)&b->rows, pa::msm_prepared_rows_bytes(n));
+    if (e == hipSuccess) e = hipMalloc((void**)&scratch, bad_off + sizeof(uint32_t));
+    uint32_t* dbad = reinterpret_cast<uint32_t*>(scratch + bad_off);
+    if (e == hipSuccess) e = pa::launch_subgroup_check(1, (const uint64_t*)bases, n, scratch, s);
+    if (e == hipSuccess) e = pa::launch_msm_prepare_g1((const uint64_t*)bases, scratch, n, b->rows, dbad, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, s);
+    const hipError_t sync = hipStreamSynchronize(s);   // also before the scratch goes, whatever failed above
+    if (e == hipSuccess) e = sync;
+    if (scratch) (void)hipFree(scratch);
+    if (e != hipSuccess) {
+        if (b->rows) (void)hipFree(b->rows);
+        delete b;
+        return fail(hip_code(e), "prepare multiexp bases", e);
+    }
+    b->in_subgroup = bad == 0 ? 1 : 0;
+    *out = b;
+    return PA_OK;
+}
+int pa_g1_msm_bases_prepare(const pa_g1_affine* bases, size_t n, pa_g1_msm_bases** out) {
+    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    *out = nullptr;
+    if (n && !bases) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n >= pa::kMsmPreparedMax) return fail(PA_ERR_INVALID_ARGUMENT, "prepared multiexp bases support n < 2^30");
+    DevBuf db;
+    int rc;
+    if ((rc = upload(db, bases, sizeof(pa_g1_affine) * n))) return rc;
+    return pa_g1_msm_bases_prepare_device(db.as<pa_g1_affine>(), n, call_stream(), out);
+}
+size_t pa_g1_msm_bases_len(const pa_g1_msm_bases* b) { return b ? b->n : 0; }
+int pa_g1_msm_bases_in_subgroup(const pa_g1_msm_bases* b) { return b ? b->in_subgroup : 0; }
+int pa_g1_msm_bases_free(pa_g1_msm_bases* b) {
+    if (!b) return PA_OK;
+    const hipError_t e = b->rows ? hipFree(b->rows) : hipSuccess;
+    delete b;
+    if (e != hipSuccess) return fail(hip_code(e), "free multiexp bases", e);
+    return PA_OK;
+}
+size_t pa_g1_multiexp_prepared_workspace_bytes(const pa_g1_msm_bases* b, size_t m) {
+    return b && m <= b->n ? pa::msm_prepared_workspace_bytes(m, b->in_subgroup != 0) : 0;
+}
+int pa_g1_multiexp_prepared_device(const pa_g1_msm_bases* b, const pa_fr_repr* scalars, size_t m, pa_g1* out,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (!b || !out || (m && (!scalars || !workspace))) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (m > b->n) return fail(PA_ERR_INVALID_ARGUMENT, "more scalars than prepared bases");
+    if (m && workspace_bytes < pa::msm_prepared_workspace_bytes(m, b->in_subgroup != 0))
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_g1_multiexp_prepared_workspace_bytes");
+    int dev = 0;
+    PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
+    if (dev != b->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the prepared bases");
+    PA_TRY(pa::launch_msm_prepared_g1(b->rows, b->n, b->in_subgroup != 0, (const uint64_t*)scalars, m, (uint64_t*)out,
+                                      workspace, workspace_bytes, (hipStream_t)stream),
+           "kernel launch");
+    return PA_OK;
+}
+int pa_g1_multiexp_prepared(const pa_g1_msm_bases* b, const pa_fr_repr* scalars, size_t m, pa_g1* out) {
+    if (!b || !out || (m && !scalars)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (m > b->n) return fail(PA_ERR_INVALID_ARGUMENT, "more scalars than prepared bases");
+    DevBuf ds, dout, dws;
+    int rc;
+    if ((rc = upload(ds, scalars, sizeof(pa_fr_repr) * m))) return rc;
+    PA_TRY(dout.alloc(sizeof(pa_g1)), "device scratch");
+    const size_t ws = pa::msm_prepared_workspace_bytes(m, b->in_subgroup != 0);
+    PA_TRY(dws.alloc(ws), "device scratch");
+    if ((rc = pa_g1_multiexp_prepared_device(b, ds.as<pa_fr_repr>(), m, dout.as<pa_g1>(), dws.p, ws, call_stream())))
+        return rc;
+    PA_TRY(call_sync(), "kernel execution");
+    return download(out, dout, sizeof(pa_g1));
+}
+
 // ---- CurveProjective / CurveAffine surface, G1 and G2 (kernels_group.hip) ----
 namespace {
 constexpr size_t jac_bytes(int group) { return group == 1 ? sizeof(pa_g1) : sizeof(pa_g2); }

@@ -22,6 +22,7 @@
 
 #include "curve_fl.h"
 #include "dec_quad.h"
+#include "glv_split.h"
 #include "launch.h"
 #include "pairing.h"
 
@@ -46,7 +47,6 @@ constexpr int kNormChunk = 8;         // points per lane in batch_normalization 
 constexpr int kGlvWindows = 17;
 constexpr int kTableRows = 2 * kGlvWindows;   // >= kCombWindows
 static_assert(kTableRows >= kCombWindows, "table rows");
-constexpr uint64_t kX2Lo = 0x0000000100000000ull, kX2Hi = 0xac45a4010001a402ull;   // x^2 = 0xd201000000010000^2
 // beta (a primitive cube root of unity in Fq, Montgomery R = 2^384), the decode kernel's kBeta
 __constant__ const uint64_t kGlvBeta[6] = {0x30f1361b798a64e8ULL, 0xf3b8ddab7ece5a2aULL, 0x16a8ca3ac61577f7ULL,
                                            0xc26a2ff874fd029bULL, 0x3636b76660701c6eULL, 0x051ba4ab241b6160ULL};
@@ -317,40 +317,16 @@ __global__ void __launch_bounds__(64) k_g1_glv_check(const uint64_t* __restrict_
     if (lane == 0) *flag = glv;
 }
 
-// s = q x^2 + rem for a 256-bit s (Barrett, HAC 14.42 without the final
-// corrections): q = floor(floor(s / 2^127) m / 2^129), m = floor(2^256 / x^2),
-// never above floor(s / x^2), so rem = s - q x^2 is in [0, 2 x^2) < 2^129
-// (one correction short at most) and q < 2^129: 17 signed base-256 digits each.
-PA_DEV void glv_split(const uint64_t s[4], uint64_t rem[3], uint64_t q[3]) {
-    constexpr uint64_t m[3] = {0x63f6e522f6cfee2eull, 0x7c6becf1e01faaddull, 1};
-    const uint64_t t[3] = {(s[1] >> 63) | (s[2] << 1), (s[2] >> 63) | (s[3] << 1), s[3] >> 63};
-    uint64_t pr[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        uint64_t c = 0;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const unsigned __int128 v = (unsigned __int128)t[i] * m[j] + pr[i + j] + c;
-            pr[i + j] = (uint64_t)v;
-            c = (uint64_t)(v >> 64);
-        }
-        pr[i + 3] = c;
-    }
-    q[0] = (pr[2] >> 1) | (pr[3] << 63);
-    q[1] = (pr[3] >> 1) | (pr[4] << 63);
-    q[2] = (pr[4] >> 1) | (pr[5] << 63);
-    // q x^2 mod 2^192
-    const unsigned __int128 a0 = (unsigned __int128)q[0] * kX2Lo;
-    const unsigned __int128 a1 = (unsigned __int128)q[0] * kX2Hi + (uint64_t)(a0 >> 64);
-    const unsigned __int128 b1 = (unsigned __int128)q[1] * kX2Lo + (uint64_t)a1;
-    const uint64_t w0 = (uint64_t)a0, w1 = (uint64_t)b1;
-    const uint64_t w2 = (uint64_t)(a1 >> 64) + (uint64_t)(b1 >> 64) + q[1] * kX2Hi + q[2] * kX2Lo;
-    unsigned __int128 d = (unsigned __int128)s[0] - w0;
-    rem[0] = (uint64_t)d;
-    d = (unsigned __int128)s[1] - w1 - (uint64_t)((d >> 64) & 1);
-    rem[1] = (uint64_t)d;
-    rem[2] = s[2] - w2 - (uint64_t)((d >> 64) & 1);
-}
+// glv_split (s = q x^2 + rem, glv_split.h) is shared with the MSM over
+// prepared bases.  Its constants are restated here, where the comb's CPU model
+// (tests/test_glv_model.py) reads them, and tied to the shipped ones.
+namespace glv_pin {
+constexpr uint64_t kX2Lo = 0x0000000100000000ull, kX2Hi = 0xac45a4010001a402ull;
+constexpr uint64_t m[3] = {0x63f6e522f6cfee2eull, 0x7c6becf1e01faaddull, 1};
+static_assert(kX2Lo == kGlvX2Lo && kX2Hi == kGlvX2Hi, "x^2 words differ from glv_split.h");
+static_assert(m[0] == kGlvBarrett[0] && m[1] == kGlvBarrett[1] && m[2] == kGlvBarrett[2],
+              "Barrett constant differs from glv_split.h");
+}  // namespace glv_pin
 
 // next signed base-256 digit of a little-endian 3-word value (window `win`)
 PA_DEV int glv_digit(const uint64_t v[3], int win, int& carry) {

@@ -34,12 +34,22 @@
 // reduction (4's fix-up, 5, 6) and its Horner leg run on side streams while
 // the next part accumulates, so only the last part's tail is exposed.
 // Work: n*W mixed additions + ~2*W*2^(c-1) additions + ~256 doublings.
+//
+// MSM over prepared G1 bases (launch_msm_prepare_g1 / launch_msm_prepared_g1):
+// the bases are converted to the lazy rows once, row n + i = -phi(P_i) =
+// (beta x_i, -y_i) beside row i = P_i, and checked for G1 membership once.
+// When every base is in G1, k_msm_digits_glv splits each scalar s = q x^2 + rem
+// (glv_split.h) into the two virtual terms rem * P_i + q * (-phi(P_i)), both
+// below 2^129, and steps 2-7 run over 2m virtual terms and ceil(130 / c)
+// windows: the same msm_run with another digit kernel, term count and window
+// count (MsmJob).  Otherwise the 257-bit pipeline runs over rows [0, m).
 
 #include <vector>
 
 #include "curve_fl.h"
 #include "curve_fl2.h"
 #include "dec_quad.h"
+#include "glv_split.h"
 #include "launch_msm.h"
 
 #include <cstdlib>
@@ -111,7 +121,7 @@ struct MsmPlan {
     uint32_t passes;            // counting-sort passes over the c-1 magnitude bits
     uint32_t T;                 // items per lane of the bucket accumulation
     uint32_t tpw;               // sort tiles per window
-    size_t items;               // W * n
+    size_t items;               // W * nt
     size_t off_keys_in, off_keys_out, off_vals_in, off_vals_out, off_start, off_end;
     size_t off_buckets, off_segs, off_tmp, off_hist, off_wtot, off_cont, off_basefl, off_hacc, off_long;
     size_t total;
@@ -129,6 +139,29 @@ static inline uint32_t msm_window_bits(size_t n) {
     if (c < 4) c = 4;
     if (c > cmax) c = cmax;
     return (uint32_t)c;
+}
+
+// The GLV path's window bits for nt = 2m virtual terms of 130 bits each
+// (PA_MSM_GLV_C to A/B an absolute value), chosen by A/B at 2^16 / 2^18 / 2^20
+// terms (profiles/msm_prepared/): the plain rule lg(nt) - 3 up to 13, where
+// 10 windows cover the 130 bits exactly and the top window's digits are as
+// spread as the others'; 13 up to 2^19 virtual terms (2^18 terms: 2.76 ms
+// against 2.97 / 3.09 / 3.09 / 3.03 for c = 14 .. 17); then 15 (9 windows) and
+// from 2^21 virtual terms 17 (8 windows: 8 x 2^21 items against the plain
+// path's 17 x 2^20; 16 has 9 windows of 2^16 / 2 buckets, 6.75 ms against 6.03).
+static inline uint32_t msm_window_bits_glv(size_t nt) {
+    static const int env = [] {
+        const char* v = getenv("PA_MSM_GLV_C");
+        const int k = v ? atoi(v) : 0;
+        return k < 4 || k > 20 ? 0 : k;
+    }();
+    if (env) return (uint32_t)env;
+    int lg = 0;
+    while (lg < 40 && ((size_t)1 << (lg + 1)) <= nt) lg++;
+    if (lg >= 21) return 17;
+    if (lg >= 20) return 15;
+    const int c = lg - 3;
+    return (uint32_t)(c < 4 ? 4 : (c > 13 ? 13 : c));
 }
 
 // items (sorted (bucket, term) pairs) per lane of the bucket accumulation
@@ -159,6 +192,23 @@ constexpr uint32_t kMsmMaxParts = 8;
 // when every bucket of every window is that long (at most ~2 100 of them at
 // 2^20 terms)
 constexpr size_t kMsmLongSpan = 128;
+// The GLV path's threshold (PA_MSM_GLV_LONGSPAN to A/B).  Its top window holds
+// the 8-10 leading bits of halves below 2^129: a few hundred buckets of
+// thousands of items each, 20-128 chunks apiece, which one lane of
+// k_msm_bucket_fix folded in 1-2.3 ms (2^18 terms at c = 15: 2.27 ms against
+// 0.56 ms for the part's whole accumulation; profiles/msm_prepared/).  128 /
+// 32 / 16 / 8 / 4 measured 6.32 / 6.06 / 6.18 / 6.03 / 6.07 ms at 2^20 terms and
+// 2.36 / 2.37 / 1.90 / 1.90 / 2.14 ms at 2^16: 8, and never below twice an
+// evenly filled bucket's span (msm_run), so that large MSMs whose every
+// bucket spans several chunks keep the one-lane fold.
+static size_t msm_long_span_glv() {
+    static const size_t v = [] {
+        const char* e = getenv("PA_MSM_GLV_LONGSPAN");
+        const long k = e ? atol(e) : 0;
+        return (size_t)(k >= 1 && k <= 4096 ? k : 8);
+    }();
+    return v;
+}
 constexpr unsigned kMsmLongBlocks = 256;
 // counting sort: a tile is 16 rounds of one item per thread of a 256-thread block
 constexpr uint32_t kSortIpt = 16;
@@ -178,9 +228,12 @@ static uint32_t msm_parts(uint32_t W) {
     return parts < W ? parts : W;
 }
 
-static hipError_t msm_plan(MsmPlan& p, int group, size_t n) {
-    p.c = msm_window_bits(n);
-    p.W = (257 + p.c - 1) / p.c;
+// `n` terms per window; the windows cover 257 bits for the plain entries (a
+// 256-bit FrRepr and the last carry), 130 for the GLV halves (glv; < 2^129).
+// own_basefl: the workspace holds the per-call converted bases.
+static hipError_t msm_plan(MsmPlan& p, int group, size_t n, bool glv = false, bool own_basefl = true) {
+    p.c = glv ? msm_window_bits_glv(n) : msm_window_bits(n);
+    p.W = ((glv ? 130 : 257) + p.c - 1) / p.c;
     p.B = 1u << (p.c - 1);
     // A/B knob: PA_MSM_SEG; default 8 buckets per segment for G1, 4 for G2 (G2
     // at 2^16 / 2^18: 5.91 / 9.13 ms with 8, 5.73 / 8.90 with 4; G1 at 2^20: 173
@@ -210,7 +263,7 @@ static hipError_t msm_plan(MsmPlan& p, int group, size_t n) {
     p.off_tmp = off; off = align256(off + jw * nseg);
     p.T = msm_chunk(p.items, msm_parts(p.W));
     p.off_cont = off; off = align256(off + jw * ((p.items + p.T - 1) / p.T + 1));
-    p.off_basefl = off; off = align256(off + 4 * (group == 1 ? 28 : 56) * n);
+    p.off_basefl = off; off = align256(off + (own_basefl ? 4 * (group == 1 ? 28 : 56) * n : 0));
     p.off_hist = off; off = align256(off + 4 * (size_t)p.W * 256 * p.tpw);
     p.off_wtot = off; off = align256(off + 4 * (size_t)p.W);
     p.off_hacc = off; off = align256(off + jw * kMsmMaxParts);
@@ -256,6 +309,62 @@ __global__ void __launch_bounds__(256) k_msm_digits(const uint64_t* __restrict__
             const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
             keys[at] = w * B + (mag - 1);
             vals[at] = (uint32_t)i | (d < 0 ? 0x80000000u : 0u);
+        }
+    }
+}
+
+// The GLV path's digits: scalar i = q x^2 + rem gives virtual term i (rem,
+// row i of the prepared bases) and virtual term m + i (q, row row_off + i =
+// -phi(P_i)); same items as k_msm_digits, nt = 2m terms per window.  Both
+// halves are below 2^129 and c W >= 130, so the top window's raw digit is
+// below 2^(c-1): with the carry at most B, never a carry out.
+__global__ void __launch_bounds__(256) k_msm_digits_glv(const uint64_t* __restrict__ scalars, size_t m,
+                                                        uint32_t row_off, uint32_t c, uint32_t W, uint32_t B,
+                                                        uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    uint64_t k[4], half[2][3];
+#pragma unroll
+    for (int w = 0; w < 4; w++) k[w] = scalars[4 * i + w];
+    glv_split(k, half[0], half[1]);
+    const uint32_t sentinel = W * B;
+    const uint32_t mask = (1u << c) - 1;
+    const size_t nt = 2 * m;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const uint64_t v0 = half[h][0], v1 = half[h][1], v2 = half[h][2];
+        const size_t term = h ? m + i : i;
+        const uint32_t row = (uint32_t)(h ? row_off + i : i);
+        uint32_t carry = 0;
+        for (uint32_t w = 0; w < W; w++) {
+            const uint32_t bit = w * c;
+            uint32_t raw = 0;
+            if (bit < 192) {
+                const uint32_t word = bit >> 6, sh = bit & 63;
+                const uint64_t lo = word == 0 ? v0 : (word == 1 ? v1 : v2);
+                const uint64_t hi = word == 0 ? v1 : (word == 1 ? v2 : 0);
+                uint64_t v = lo >> sh;
+                if (sh + c > 64) v |= hi << (64 - sh);
+                raw = (uint32_t)v & mask;
+            }
+            raw += carry;
+            int d;
+            if (raw > B) {
+                d = (int)raw - (int)(1u << c);
+                carry = 1;
+            } else {
+                d = (int)raw;
+                carry = 0;
+            }
+            const size_t at = (size_t)w * nt + term;
+            if (d == 0) {
+                keys[at] = sentinel;
+                vals[at] = row;
+            } else {
+                const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+                keys[at] = w * B + (mag - 1);
+                vals[at] = row | (d < 0 ? 0x80000000u : 0u);
+            }
         }
     }
 }
@@ -557,6 +666,37 @@ __global__ void __launch_bounds__(256) k_msm_bases_fl(const uint64_t* __restrict
     }
 }
 
+// The prepared rows (launch_msm_prepare_g1): row i as k_msm_bases_fl writes
+// it, row n + i = -phi(P_i) = (beta x_i, -y_i), an infinity base flagged in
+// both; the membership flags ok[i] (launch_subgroup_check) counted into *bad.
+// beta: kernels_curve.hip's kGlvBeta, the decode kernel's kBeta (Montgomery words)
+__constant__ const uint64_t kMsmBeta[6] = {0x30f1361b798a64e8ULL, 0xf3b8ddab7ece5a2aULL, 0x16a8ca3ac61577f7ULL,
+                                           0xc26a2ff874fd029bULL, 0x3636b76660701c6eULL, 0x051ba4ab241b6160ULL};
+__global__ void __launch_bounds__(256) k_msm_bases_prepare(const uint64_t* __restrict__ bases,
+                                                           const uint8_t* __restrict__ ok, size_t n,
+                                                           uint32_t* __restrict__ rows, uint32_t* __restrict__ bad) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Aff<Fq> a;
+    load_aff(a, bases + (size_t)Grp<1>::AW * i);
+    Fq beta, bx, ny;
+    fq_load(beta, kMsmBeta);
+    mul(bx, a.x, beta);
+    neg(ny, a.y);
+    const F<1> x = fl_from_abi(a.x), y = fl_from_abi(a.y), px = fl_from_abi(bx), py = fl_from_abi(ny);
+    const uint32_t inf = a.inf ? 0x80000000u : 0u;
+    uint32_t* d = rows + 28 * i;
+    uint32_t* e = rows + 28 * (n + i);
+#pragma unroll
+    for (int k = 0; k < 14; k++) {
+        d[k] = x.w[k] | (k == 13 ? inf : 0u);
+        d[14 + k] = y.w[k];
+        e[k] = px.w[k] | (k == 13 ? inf : 0u);
+        e[14 + k] = py.w[k];
+    }
+    if (!ok[i]) atomicAdd(bad, 1u);
+}
+
 PA_DEV void msm_flush_fl(uint32_t key, const FlJac& acc, bool untouched, size_t j0, size_t k,
                          const uint32_t* __restrict__ start, uint64_t* __restrict__ buckets,
                          uint64_t* __restrict__ cont) {
@@ -684,7 +824,7 @@ __global__ void __launch_bounds__(64) k_msm_bucket_fix(const uint32_t* __restric
                                                        uint32_t T, const uint64_t* __restrict__ cont,
                                                        uint64_t* __restrict__ buckets,
                                                        uint32_t* __restrict__ long_list,
-                                                       uint32_t* __restrict__ long_count) {
+                                                       uint32_t* __restrict__ long_count, size_t long_span) {
     using F = typename Grp<G>::F;
     constexpr int JW = Grp<G>::JW;
     const size_t b = b0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -698,7 +838,7 @@ __global__ void __launch_bounds__(64) k_msm_bucket_fix(const uint32_t* __restric
     }
     const size_t first = s / T, last = (e - 1) / T;
     if (first == last) return;
-    if (long_list && last - first > kMsmLongSpan) {   // k_msm_long_fix folds it, a block per bucket
+    if (long_list && last - first > long_span) {   // k_msm_long_fix folds it, a block per bucket
         long_list[atomicAdd(long_count, 1u)] = (uint32_t)b;
         return;
     }
@@ -1173,6 +1313,13 @@ size_t msm_workspace_bytes(int group, size_t n) {
     if (msm_plan(p, group, n) != hipSuccess) return 0;
     return p.total;
 }
+size_t msm_prepared_rows_bytes(size_t n) { return 2 * n * 28 * sizeof(uint32_t); }
+size_t msm_prepared_workspace_bytes(size_t m, bool glv) {
+    if (m == 0) return 0;
+    MsmPlan p;
+    if (msm_plan(p, 1, glv ? 2 * m : m, glv, false) != hipSuccess) return 0;
+    return p.total;
+}
 
 // two non-blocking side streams per device (bucket reduction, Horner legs),
 // created on the device of the caller's stream.  They are shared by every
@@ -1207,16 +1354,30 @@ static hipError_t msm_side_streams(hipStream_t caller, hipStream_t out[2]) {
     return hipSuccess;
 }
 
+// What one MSM sums: `terms` scalars over affine ABI records converted per call
+// (bases; the plain entries), or over prepared lazy rows (rows, G1): the
+// 257-bit digits over rows [0, terms), or with glv the two virtual terms per
+// scalar over rows i and row_off + i.
+struct MsmJob {
+    const uint64_t* bases;
+    const uint32_t* rows;
+    const uint64_t* scalars;
+    size_t terms;
+    size_t row_off;
+    bool glv;
+};
+
 template <int G>
-static hipError_t msm_run(const uint64_t* bases, const uint64_t* scalars, size_t n, uint64_t* out, void* ws,
-                          size_t ws_bytes, hipStream_t s) {
+static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_bytes, hipStream_t s) {
     constexpr int JW = Grp<G>::JW;
-    if (n == 0) {
+    if (job.terms == 0) {
         hipLaunchKernelGGL(k_jac_zero_out<G>, dim3(1), dim3(64), 0, s, out);
         return hipGetLastError();
     }
+    const uint64_t* bases = job.bases;
+    const size_t n = job.glv ? 2 * job.terms : job.terms;   // items per window
     MsmPlan p;
-    hipError_t e = msm_plan(p, G, n);
+    hipError_t e = msm_plan(p, G, n, job.glv, job.rows == nullptr);
     if (e != hipSuccess) return e;
     if (ws_bytes < p.total || !ws) return hipErrorInvalidValue;
     if (p.items > 0xffffffffull) return hipErrorInvalidValue;  // 32-bit item positions
@@ -1232,8 +1393,12 @@ static hipError_t msm_run(const uint64_t* bases, const uint64_t* scalars, size_t
     uint64_t* tmp = reinterpret_cast<uint64_t*>(base + p.off_tmp);
     const size_t nb = (size_t)p.W * p.B;
 
-    hipLaunchKernelGGL(k_msm_digits, dim3(msm_blocks(n, 256)), dim3(256), 0, s, scalars, n, p.c, p.W, p.B, keys_in,
-                       vals_in);
+    if (job.glv)
+        hipLaunchKernelGGL(k_msm_digits_glv, dim3(msm_blocks(job.terms, 256)), dim3(256), 0, s, job.scalars, job.terms,
+                           (uint32_t)job.row_off, p.c, p.W, p.B, keys_in, vals_in);
+    else
+        hipLaunchKernelGGL(k_msm_digits, dim3(msm_blocks(n, 256)), dim3(256), 0, s, job.scalars, n, p.c, p.W, p.B,
+                           keys_in, vals_in);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // the bucketing sort: ping-pong between the _in and _out arrays; the last
     // destination's tail past the nonzero items is set to sentinel keys first
@@ -1258,11 +1423,13 @@ static hipError_t msm_run(const uint64_t* bases, const uint64_t* scalars, size_t
                        p.W * p.B, start, end);
     uint64_t* cont = reinterpret_cast<uint64_t*>(base + p.off_cont);
     uint64_t* hacc = reinterpret_cast<uint64_t*>(base + p.off_hacc);
-    const uint32_t* basefl = reinterpret_cast<const uint32_t*>(base + p.off_basefl);
+    const uint32_t* basefl = job.rows ? job.rows : reinterpret_cast<const uint32_t*>(base + p.off_basefl);
     // G2 on the lazy core's Fq2 (round 4); PA_MSM_G2_LAZY=0: the 12-word kernels (A/B)
     static const bool g2_lazy_env = !getenv("PA_MSM_G2_LAZY") || atoi(getenv("PA_MSM_G2_LAZY")) != 0;
     const bool g2_lazy = G == 2 && g2_lazy_env;
-    if constexpr (G == 1)
+    if (job.rows) {
+        if (G != 1) return hipErrorInvalidValue;   // prepared rows are G1's
+    } else if constexpr (G == 1)
         hipLaunchKernelGGL(k_msm_bases_fl, dim3(msm_blocks(n, 256)), dim3(256), 0, s, bases, n,
                            reinterpret_cast<uint32_t*>(base + p.off_basefl));
     else if (g2_lazy)
@@ -1311,6 +1478,11 @@ static hipError_t msm_run(const uint64_t* bases, const uint64_t* scalars, size_t
     uint32_t* long_list = reinterpret_cast<uint32_t*>(base + p.off_long);
     uint32_t* long_count = long_list + nb;
     const bool lazy = G == 1 || g2_lazy;
+    size_t long_span = kMsmLongSpan;
+    if (job.glv) {
+        const size_t even = 2 * (n / ((size_t)p.B * p.T) + 1);
+        long_span = msm_long_span_glv() > even ? msm_long_span_glv() : even;
+    }
     // segment sums -> one per window, `group` at a time, windows [w0, w1)
     auto group_levels = [&](uint32_t w0, uint32_t w1, hipStream_t st) {
         uint64_t *src = segs, *dst = tmp;
@@ -1337,10 +1509,10 @@ static hipError_t msm_run(const uint64_t* bases, const uint64_t* scalars, size_t
         if (lazy && (r = hipMemsetAsync(long_count + q, 0, 4, st)) != hipSuccess) return r;
         if (lazy)
             hipLaunchKernelGGL((k_msm_bucket_fix<G, true>), dim3(msm_blocks(b1 - b0, 64)), dim3(64), 0, st, start, end,
-                               b0, b1, p.T, cont, buckets, long_list + b0, long_count + q);
+                               b0, b1, p.T, cont, buckets, long_list + b0, long_count + q, long_span);
         else
             hipLaunchKernelGGL((k_msm_bucket_fix<G, false>), dim3(msm_blocks(b1 - b0, 64)), dim3(64), 0, st, start,
-                               end, b0, b1, p.T, cont, buckets, nullptr, long_count + q);
+                               end, b0, b1, p.T, cont, buckets, nullptr, long_count + q, long_span);
         if (lazy)
             hipLaunchKernelGGL(k_msm_long_fix<G>, dim3(kMsmLongBlocks), dim3(LazyJac<G>::NT), 0, st, start, end, p.T,
                                cont, buckets, long_list + b0, long_count + q);
@@ -1459,8 +1631,24 @@ static hipError_t msm_run(const uint64_t* bases, const uint64_t* scalars, size_t
 hipError_t launch_msm(int group, const uint64_t* bases, const uint64_t* scalars, size_t n, uint64_t* out, void* ws,
                       size_t ws_bytes, hipStream_t stream) {
     if (n >= 0x80000000ull) return hipErrorInvalidValue;
-    return group == 1 ? msm_run<1>(bases, scalars, n, out, ws, ws_bytes, stream)
-                      : msm_run<2>(bases, scalars, n, out, ws, ws_bytes, stream);
+    const MsmJob job{bases, nullptr, scalars, n, 0, false};
+    return group == 1 ? msm_run<1>(job, out, ws, ws_bytes, stream) : msm_run<2>(job, out, ws, ws_bytes, stream);
+}
+
+hipError_t launch_msm_prepare_g1(const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows, uint32_t* bad,
+                                 hipStream_t stream) {
+    if (n >= kMsmPreparedMax) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess || n == 0) return e;
+    hipLaunchKernelGGL(k_msm_bases_prepare, dim3(msm_blocks(n, 256)), dim3(256), 0, stream, bases, ok, n, rows, bad);
+    return hipGetLastError();
+}
+
+hipError_t launch_msm_prepared_g1(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
+                                  uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream) {
+    if (len >= kMsmPreparedMax || m > len) return hipErrorInvalidValue;
+    const MsmJob job{nullptr, rows, scalars, m, len, glv};
+    return msm_run<1>(job, out, ws, ws_bytes, stream);
 }
 
 hipError_t launch_scalar_mul(int group, int projective, const uint64_t* p, const uint64_t* scalars, size_t n,

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, _lib, call
+from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, G1MsmBases, _lib, call
 
 
 def _stream_ptr(stream):
@@ -291,6 +291,33 @@ def multiexp(group, bases, scalars, out, workspace, stream=None):
     call("pa_g%d_multiexp_device" % group, _dptr(bases, aw, "bases"), _dptr(scalars, 4, "scalars"),
          bases.shape[0], _dptr(out, jw, "out"), ctypes.c_void_p(workspace.data_ptr()), workspace.numel(),
          _stream_ptr(stream))
+
+
+def msm_prepare(bases, stream=None):
+    """Prepare G1 multiexp bases resident in HBM ((n, 13) affine records) once:
+    the membership check and the conversion the plain multiexp repeats per call.
+    Synchronizes the stream.  Returns a G1MsmBases (len, in_subgroup, close())
+    tied to the tensor's device; `bases` may be released afterwards."""
+    n = bases.shape[0]
+    h = ctypes.c_void_p(0)
+    call("pa_g1_msm_bases_prepare_device", _dptr(bases, W_G1A, "bases"), n, _stream_ptr(stream), ctypes.byref(h))
+    return G1MsmBases._adopt(h)
+
+
+def multiexp_prepared_workspace(prepared, m, device):
+    """A device workspace sized for multiexp_prepared over the first m prepared bases."""
+    nbytes = int(_lib.pa_g1_multiexp_prepared_workspace_bytes(prepared.check_terms(int(m)), int(m)))
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
+def multiexp_prepared(prepared, scalars, out, workspace, stream=None):
+    """out (1, 18) = sum_i scalars[i] * P_i over the first m = len(scalars) prepared
+    bases (FrRepr (m, 4)), equal as a point to multiexp(1, ...) over the same bases."""
+    m = scalars.shape[0]
+    h = prepared.check_terms(m)
+    _rows(out, 1, "out")
+    call("pa_g1_multiexp_prepared_device", h, _dptr(scalars, 4, "scalars"), m, _dptr(out, W_G1, "out"),
+         ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
 
 
 def wnaf_exact_workspace(group, n, window, fixed_scalar, device):
