@@ -328,6 +328,18 @@ int pa_fq2_sqrt_batch(const pa_fq2 *a, pa_fq2 *out, uint8_t *ok, size_t n);
  * Miller value is zero (None). */
 int pa_multi_miller_loop_affine(const pa_g1_affine *p, const pa_g2_affine *q, size_t n, pa_fq12 *out);
 int pa_multi_pairing(const pa_g1_affine *p, const pa_g2_affine *q, size_t n, pa_fq12 *out, uint8_t *ok);
+/* m independent pa_multi_pairing products in one call -- a batch of signature
+ * or proof checks: n Miller loops, a segmented product, m final
+ * exponentiations.  `offsets` is CSR over the pairs, in host memory: m + 1
+ * entries, offsets[0] == 0, non-decreasing, n = offsets[m]; product j covers
+ * pairs [offsets[j], offsets[j+1]).  (out[j], ok[j]) are bit-identical to
+ * pa_multi_pairing on that segment alone (an empty product is one with
+ * ok = 1); is_one[j] = ok[j] && out[j] == one, the verifier's answer.  `out`
+ * may be NULL if `is_one` is not (then only the 2 m flag bytes come back);
+ * `is_one` may be NULL.  Offsets that are not CSR give PA_ERR_INVALID_ARGUMENT
+ * before anything is launched.  m == 0 is a no-op. */
+int pa_multi_pairing_batch(const pa_g1_affine *p, const pa_g2_affine *q, const uint64_t *offsets, size_t m,
+                           pa_fq12 *out, uint8_t *ok, uint8_t *is_one);
 /* pa_pairing_batch split over devices 0..ndev-1 of this process (contiguous
  * shards, one host thread per device); ndev <= pa_device_count.  The
  * environment variable PA_DEVICE_MAP (a comma list of device ordinals) maps
@@ -489,6 +501,18 @@ int pa_final_exponentiation_batch_device(const pa_fq12 *in, pa_fq12 *out, uint8_
  * pa_fq12 (the per-pair Miller values, reduced in place to their product) */
 int pa_multi_pairing_device(const pa_g1_affine *p, const pa_g2_affine *q, size_t n, pa_fq12 *out, uint8_t *ok,
                             pa_fq12 *work, void *stream);
+/* pa_multi_pairing_batch on device memory: p, q (n = host_offsets[m] records),
+ * out (m records), ok and is_one (m bytes; is_one may be NULL) and `workspace`
+ * (pa_multi_pairing_batch_workspace_bytes(n, m) bytes: the Miller values, the
+ * products and the staged offsets; exact, monotone in both arguments) are
+ * device pointers; `host_offsets` is host memory (call metadata, like n) and
+ * is not read after the call returns.  Everything is enqueued on `stream`; the
+ * call waits only until the offsets have been staged, not for the kernels, and
+ * never allocates device memory.  Not for stream capture. */
+size_t pa_multi_pairing_batch_workspace_bytes(size_t n_pairs, size_t m);
+int pa_multi_pairing_batch_device(const pa_g1_affine *p, const pa_g2_affine *q, const uint64_t *host_offsets,
+                                  size_t m, pa_fq12 *out, uint8_t *ok, uint8_t *is_one, void *workspace,
+                                  void *stream);
 /* G2Prepared::from_affine (mod.rs:168-358) and miller_loop over (G1Affine,
  * G2Prepared) pairs (mod.rs:40-102) on device records: the north-star form
  * whose line coefficients are materialized in HBM (19 592 B per point).

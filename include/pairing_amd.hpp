@@ -727,6 +727,32 @@ struct Bls12 {
               "Bls12::multi_pairing");
         return ok ? std::optional<Fq12>(r) : std::nullopt;
     }
+    // m independent multi_pairing products in one call -- a batch of signature
+    // or proof checks (pa_multi_pairing_batch).  Product j covers pairs
+    // offsets[j] .. offsets[j+1]: CSR, m + 1 entries from 0 to p.size().
+    // values[j] / ok[j] are multi_pairing's for that segment (ok[j] = 0 for
+    // None), is_one[j] = ok[j] && values[j] == one; with want_values = false
+    // `values` stays empty and only the flags come back from the device.
+    struct MultiPairingBatch {
+        std::vector<Fq12> values;
+        std::vector<uint8_t> ok, is_one;
+    };
+    static MultiPairingBatch multi_pairing_batch(const std::vector<G1Affine>& p, const std::vector<G2Affine>& q,
+                                                 const std::vector<uint64_t>& offsets, bool want_values = true) {
+        if (p.size() != q.size()) throw Error(PA_ERR_INVALID_ARGUMENT, "multi_pairing_batch: length mismatch");
+        if (offsets.empty() || offsets.back() != p.size())
+            throw Error(PA_ERR_INVALID_ARGUMENT, "multi_pairing_batch: offsets must end at the number of pairs");
+        const size_t m = offsets.size() - 1;
+        MultiPairingBatch r;
+        r.ok.resize(m);
+        r.is_one.resize(m);
+        if (want_values) r.values.resize(m);
+        if (m)
+            check(pa_multi_pairing_batch(p.empty() ? nullptr : &p[0].v, q.empty() ? nullptr : &q[0].v, offsets.data(), m,
+                                         want_values ? &r.values[0].v : nullptr, r.ok.data(), r.is_one.data()),
+                  "Bls12::multi_pairing_batch");
+        return r;
+    }
 };
 
 inline Fq12 G1Affine::pairing_with(const G2Affine& other) const { return Bls12::pairing(*this, other); }

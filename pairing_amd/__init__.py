@@ -17,7 +17,7 @@ Device-resident entry points for torch tensors live in `pairing_amd.device`.
 import numpy as np
 
 from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, G1MsmBases, PairingError, _lib,
-                      as_rows, call, device_count, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
+                      as_rows, call, csr_offsets, device_count, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
 
 __all__ = [
     "PairingError", "version", "device_count", "set_device", "set_pairing_kernel", "set_decode_kernel",
@@ -27,7 +27,7 @@ __all__ = [
     "fq2_inverse", "fq2_frobenius_map", "fq6_square", "fq6_inverse", "fq6_frobenius_map", "fq_pow", "fq12_pow",
     "g1_batch_normalization", "g1_wnaf_fixed_base",
     "g2_prepare", "miller_loop_batch", "miller_loop_shared_prepared", "multi_miller_loop", "final_exponentiation", "pairing",
-    "multi_miller_loop_affine", "multi_pairing", "pairing_multi_gpu",
+    "multi_miller_loop_affine", "multi_pairing", "multi_pairing_batch", "pairing_multi_gpu",
     "fq_sqrt", "fq2_sqrt", "g1_decode", "g2_decode", "g1_encode", "g2_encode", "DECODE_STATUS",
     "g1_subgroup_check", "g2_subgroup_check",
     "fr_mul", "fr_square", "fr_add", "fr_sub", "fr_double", "fr_negate", "fr_inverse",
@@ -366,6 +366,33 @@ def multi_pairing(p, q):
     ok = np.zeros(1, np.uint8)
     call("pa_multi_pairing", ptr(p), ptr(q), p.shape[0], ptr(out), ptr(ok))
     return out[0], bool(ok[0])
+
+
+def multi_pairing_batch(p, q, offsets=None, pairs_per_product=None, want_values=True):
+    """m independent multi_pairing products in one call -- a batch of signature or
+    proof checks.  Product j covers pairs offsets[j] .. offsets[j+1] (CSR: m + 1
+    entries from 0 to n, non-decreasing); or give pairs_per_product = k for m = n / k
+    products of k pairs each.  Returns (out, ok, is_one): out (m, 72) as multi_pairing
+    gives for each segment, or None with want_values=False (then only the flags
+    come back from the device); ok and is_one (m,) bool, is_one[j] = ok[j] and
+    out[j] == one."""
+    p, q = _pairs(p, q)
+    n = p.shape[0]
+    if (offsets is None) == (pairs_per_product is None):
+        raise ValueError("give exactly one of offsets and pairs_per_product")
+    if pairs_per_product is not None:
+        k = int(pairs_per_product)
+        if k < 1 or n % k:
+            raise ValueError("%d pairs do not split into products of %d" % (n, k))
+        offsets = np.arange(n // k + 1, dtype=np.uint64) * np.uint64(k)
+    o = csr_offsets(offsets, n)
+    m = o.shape[0] - 1
+    out = np.empty((m, W_FQ12), np.uint64) if want_values else None
+    ok = np.zeros(m, np.uint8)
+    is_one = np.zeros(m, np.uint8)
+    call("pa_multi_pairing_batch", ptr(p), ptr(q), ptr(o), m, ptr(out) if want_values else None, ptr(ok),
+         ptr(is_one))
+    return out, ok.astype(bool), is_one.astype(bool)
 
 
 def pairing_multi_gpu(p, q, ndev):

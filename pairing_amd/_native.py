@@ -175,6 +175,9 @@ for _g in (1, 2):
 _SIGS.update({
     "pa_fq2_inverse_batch": [_P, _P, _P, _N],
     "pa_multi_pairing_device": [_P, _P, _N, _P, _P, _P, _P],
+    "pa_multi_pairing_batch": [_P, _P, _P, _N, _P, _P, _P],
+    "pa_multi_pairing_batch_device": [_P, _P, _P, _N, _P, _P, _P, _P, _P],
+    "pa_multi_pairing_batch_workspace_bytes": [_N, _N],   # returns size_t (below)
     "pa_fq2_frobenius_map_batch": [_P, _P, _N, _N],
     "pa_fq6_square_batch": [_P, _P, _N],
     "pa_fq6_inverse_batch": [_P, _P, _P, _N],
@@ -204,6 +207,7 @@ _lib.pa_wnaf_exact_workspace_bytes.argtypes = [ctypes.c_int, _N, ctypes.c_int, c
 _lib.pa_wnaf_exact_workspace_bytes.restype = ctypes.c_size_t
 _lib.pa_g1_msm_bases_len.restype = ctypes.c_size_t
 _lib.pa_g1_multiexp_prepared_workspace_bytes.restype = ctypes.c_size_t
+_lib.pa_multi_pairing_batch_workspace_bytes.restype = ctypes.c_size_t
 
 
 def version():
@@ -258,6 +262,27 @@ def as_rows(a, width, name="array"):
     if a.ndim != 2 or a.shape[1] != width:
         raise ValueError("%s must have shape (n, %d), got %s" % (name, width, a.shape))
     return a
+
+
+def csr_offsets(offsets, n):
+    """The CSR offsets of multi_pairing_batch as a host uint64 array: m + 1
+    entries from 0 to n (the number of pairs), non-decreasing.  Takes a numpy
+    array or a CPU tensor of an integer type; anything else is a ValueError."""
+    if getattr(offsets, "is_cuda", False):
+        raise ValueError("offsets must be host memory (a numpy array or a CPU tensor)")
+    o = np.asarray(offsets)
+    if o.ndim != 1 or o.shape[0] < 1 or o.dtype.kind not in "iu":
+        raise ValueError("offsets must be a 1-d integer array of m + 1 entries, got %s %s" % (o.dtype, o.shape))
+    if o.dtype.kind == "i" and (o < 0).any():
+        raise ValueError("offsets must not be negative")
+    o = np.ascontiguousarray(o, dtype=np.uint64)
+    if int(o[0]) != 0:
+        raise ValueError("offsets must start at 0, got %d" % int(o[0]))
+    if (o[1:] < o[:-1]).any():
+        raise ValueError("offsets must be non-decreasing")
+    if int(o[-1]) != int(n):
+        raise ValueError("the last offset is %d, the call has %d pairs" % (int(o[-1]), int(n)))
+    return o
 
 
 class G1MsmBases:

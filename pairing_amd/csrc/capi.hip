@@ -981,6 +981,105 @@ int pa_multi_pairing(const pa_g1_affine* p, const pa_g2_affine* q, size_t n, pa_
     return download(ok, dok, 1);
 }
 
+// ---- batched multi-pairing: m independent products in one call ----
+// Workspace of the device entry: the n per-pair Miller values, the m products
+// (contiguous, what the final exponentiation reads) and the m + 1 staged offsets.
+namespace {
+struct MpbLayout {
+    size_t miller, prod, offsets, bytes;
+};
+MpbLayout mpb_layout(size_t n, size_t m) {
+    MpbLayout l;
+    l.miller = 0;
+    l.prod = sizeof(pa_fq12) * n;
+    l.offsets = l.prod + sizeof(pa_fq12) * m;
+    l.bytes = l.offsets + sizeof(uint64_t) * (m + 1);
+    return l;
+}
+// CSR check of host offsets; the longest segment through *max_len
+const char* mpb_check_offsets(const uint64_t* offsets, size_t m, size_t* max_len) {
+    if (offsets[0] != 0) return "multi_pairing_batch: offsets[0] must be 0";
+    size_t longest = 0;
+    for (size_t j = 0; j < m; j++) {
+        if (offsets[j + 1] < offsets[j]) return "multi_pairing_batch: offsets must be non-decreasing";
+        const uint64_t len = offsets[j + 1] - offsets[j];
+        if (len > longest) longest = (size_t)len;
+    }
+    if (offsets[m] > SIZE_MAX / sizeof(pa_g2_affine)) return "multi_pairing_batch: too many pairs";
+    *max_len = longest;
+    return nullptr;
+}
+}  // namespace
+
+size_t pa_multi_pairing_batch_workspace_bytes(size_t n_pairs, size_t m) { return mpb_layout(n_pairs, m).bytes; }
+
+int pa_multi_pairing_batch_device(const pa_g1_affine* p, const pa_g2_affine* q, const uint64_t* host_offsets, size_t m,
+                                  pa_fq12* out, uint8_t* ok, uint8_t* is_one, void* workspace, void* stream) {
+    if (m == 0) return PA_OK;
+    if (!host_offsets || !out || !ok || !workspace) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    size_t max_len = 0;
+    if (const char* bad = mpb_check_offsets(host_offsets, m, &max_len)) return fail(PA_ERR_INVALID_ARGUMENT, bad);
+    const size_t n = (size_t)host_offsets[m];
+    if (n && (!p || !q)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    const hipStream_t s = (hipStream_t)stream;
+    const MpbLayout l = mpb_layout(n, m);
+    uint64_t* miller = (uint64_t*)((char*)workspace + l.miller);
+    uint64_t* prod = (uint64_t*)((char*)workspace + l.prod);
+    uint64_t* dev_offsets = (uint64_t*)((char*)workspace + l.offsets);
+    if (m == 1 && n) {
+        // one product: the single-product entry, with its cooperative product paths
+        int rc = pa_multi_pairing_device(p, q, n, out, ok, (pa_fq12*)miller, stream);
+        if (rc) return rc;
+        if (is_one) PA_TRY(pa::launch_fq12_is_one((const uint64_t*)out, ok, is_one, 1, s), "kernel launch");
+        return PA_OK;
+    }
+    // The offsets go up first and the kernels are enqueued behind them; the host
+    // then waits for that copy alone (host_offsets may be pageable and is the
+    // caller's again on return), not for the kernels.
+    hipEvent_t staged = nullptr;
+    PA_TRY(hipEventCreateWithFlags(&staged, hipEventDisableTiming), "event");
+    hipError_t e = hipMemcpyAsync(dev_offsets, host_offsets, sizeof(uint64_t) * (m + 1), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipEventRecord(staged, s);
+    if (e == hipSuccess && n) e = pairing_ml_launch((const uint64_t*)p, (const uint64_t*)q, miller, n, s);
+    if (e == hipSuccess) e = pa::launch_fq12_segmented_product(miller, dev_offsets, n, m, max_len, prod, s);
+    if (e == hipSuccess) e = fe_launch(prod, (uint64_t*)out, ok, m, s);
+    if (e == hipSuccess && is_one) e = pa::launch_fq12_is_one((const uint64_t*)out, ok, is_one, m, s);
+    const hipError_t w = hipEventSynchronize(staged);
+    (void)hipEventDestroy(staged);
+    if (e != hipSuccess) return fail(hip_code(e), "kernel launch", e);
+    if (w != hipSuccess) return fail(hip_code(w), "H2D copy", w);
+    return PA_OK;
+}
+
+int pa_multi_pairing_batch(const pa_g1_affine* p, const pa_g2_affine* q, const uint64_t* offsets, size_t m,
+                           pa_fq12* out, uint8_t* ok, uint8_t* is_one) {
+    if (m == 0) return PA_OK;
+    if (!offsets || !ok || (!out && !is_one)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    size_t max_len = 0;
+    if (const char* bad = mpb_check_offsets(offsets, m, &max_len)) return fail(PA_ERR_INVALID_ARGUMENT, bad);
+    const size_t n = (size_t)offsets[m];
+    if (n && (!p || !q)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    // one stream round trip: the pairs up, the device entry, the flags (and the
+    // values, when asked for) down
+    DevBuf dp, dq, dout, dflags, dws;
+    int rc;
+    if ((rc = upload(dp, p, sizeof(pa_g1_affine) * n)) || (rc = upload(dq, q, sizeof(pa_g2_affine) * n)))
+        return rc;
+    PA_TRY(dout.alloc(sizeof(pa_fq12) * m), "device scratch");
+    PA_TRY(dflags.alloc(2 * m), "device scratch");   // ok, then is_one
+    PA_TRY(dws.alloc(mpb_layout(n, m).bytes), "device scratch");
+    uint8_t* dev_ok = dflags.as<uint8_t>();
+    const hipStream_t s = call_stream();
+    if ((rc = pa_multi_pairing_batch_device(dp.as<pa_g1_affine>(), dq.as<pa_g2_affine>(), offsets, m,
+                                            dout.as<pa_fq12>(), dev_ok, is_one ? dev_ok + m : nullptr, dws.p, s)))
+        return rc;
+    PA_TRY(hipMemcpyAsync(ok, dev_ok, m, hipMemcpyDeviceToHost, s), "D2H copy");
+    if (is_one) PA_TRY(hipMemcpyAsync(is_one, dev_ok + m, m, hipMemcpyDeviceToHost, s), "D2H copy");
+    if (out) PA_TRY(hipMemcpyAsync(out, dout.p, sizeof(pa_fq12) * m, hipMemcpyDeviceToHost, s), "D2H copy");
+    PA_TRY(hipStreamSynchronize(s), "kernel execution");
+    return PA_OK;
+}
+
 // ---- point encodings ----
 namespace {
 constexpr size_t enc_size(int group, int compressed) { return (group == 1 ? 48 : 96) * (compressed ? 1 : 2); }

@@ -122,6 +122,16 @@ hipError_t launch_coop_final_exp(const uint64_t* in, uint64_t* out, uint8_t* ok,
 hipError_t launch_coop_fq12_product(uint64_t* work, size_t n, uint64_t* out, hipStream_t stream);
 // out[0] = prod_i in[i] (Fq12), in-place tree reduction over `work` (n entries, clobbered)
 hipError_t launch_fq12_product(uint64_t* work, size_t n, uint64_t* out, hipStream_t stream);
+// Segmented products (kernels_segprod.hip): prod[j] = the product of
+// work[offsets[j] .. offsets[j + 1]) for j < m, one for an empty segment.
+// offsets: m + 1 device words, CSR (offsets[0] = 0, non-decreasing,
+// offsets[m] = n); max_len: the longest segment (it sets the number of halving
+// levels that run before the sequential kernel); `work` is clobbered.
+size_t segprod_serial_max();
+hipError_t launch_fq12_segmented_product(uint64_t* work, const uint64_t* offsets, size_t n, size_t m, size_t max_len,
+                                         uint64_t* prod, hipStream_t stream);
+// is_one[j] = ok[j] && out[j] == Fq12 one (canonical Montgomery words)
+hipError_t launch_fq12_is_one(const uint64_t* out, const uint8_t* ok, uint8_t* is_one, size_t m, hipStream_t stream);
 
 // point decoding / encoding (group 1 or 2; records in the wire format) and
 // square roots (degree 1: Fq, 2: Fq2), kernels_decode.hip

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, G1MsmBases, _lib, call
+from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, G1MsmBases, _lib, call, csr_offsets
 
 
 def _stream_ptr(stream):
@@ -151,6 +151,37 @@ def multi_pairing(p, q, out, ok, work, stream=None):
     _rows(work, n, "work")   # the per-pair Miller values and the product tree
     call("pa_multi_pairing_device", *args, n, _dptr(out, W_FQ12, "out"), _flags(ok, 1),
          _dptr(work, W_FQ12, "work"), _stream_ptr(stream))
+
+
+def multi_pairing_batch_workspace_words(n, m):
+    """int64 words of `work` for multi_pairing_batch over n pairs in m products."""
+    return (int(_lib.pa_multi_pairing_batch_workspace_bytes(int(n), int(m))) + 7) // 8
+
+
+def multi_pairing_batch(p, q, offsets, out, ok, is_one, work, stream=None):
+    """m independent multi_pairing products over pairs resident in HBM (a batch of
+    signature or proof checks): product j covers pairs offsets[j] .. offsets[j+1].
+    offsets: CSR, m + 1 entries from 0 to n, a CPU int64/uint64 tensor or numpy
+    array (host metadata, staged by the call); out (m, 72), ok (m,) uint8, is_one
+    (m,) uint8 or None (is_one[j] = ok[j] and out[j] == one), work an int64 buffer
+    of multi_pairing_batch_workspace_words(n, m).  Sizes and offsets are checked
+    before anything touches the device."""
+    n = p.shape[0]
+    o = csr_offsets(offsets, n)
+    m = o.shape[0] - 1
+    _rows(q, n, "q")
+    _rows(out, m, "out")
+    for t, name in ((ok, "ok"), (is_one, "is_one")):
+        if t is not None and t.numel() < m:
+            raise ValueError("%s has %d flags, the call needs %d" % (name, t.numel(), m))
+    need = multi_pairing_batch_workspace_words(n, m)
+    if work.numel() < need:
+        raise ValueError("work has %d words, the call needs %d" % (work.numel(), need))
+    if ok is None:
+        raise ValueError("ok must be a contiguous uint8 CUDA tensor of >= %d elements" % m)
+    args = (_dptr(p, W_G1A, "p"), _dptr(q, W_G2A, "q"), ctypes.c_void_p(o.ctypes.data), m,
+            _dptr(out, W_FQ12, "out"), _flags(ok, m), _flags(is_one, m, "is_one"), _words(work, need, "work"))
+    call("pa_multi_pairing_batch_device", *args, _stream_ptr(stream))
 
 
 def g1_fixed_base_table(base, stream=None):
