@@ -163,14 +163,16 @@ def macs(counts):
     one pairing, from the DSL's dynamic op counts: a K-term product leaf is
     196 (K + 1) (K products + one Montgomery reduction), a square 392 (it is
     emitted as a one-term product), red() 30; lazy reduction: a K-term wide
-    product 196 K, its reduction wred() 222 (196 + 26 column additions)."""
+    product 196 K, its reduction wred() 222 (196 + 26 column additions);
+    sopmw (a product minus a wide value, reduced) 196 + 222."""
     n = 0
     for k, v in counts.items():
         if k.startswith("sop") and k[3:].isdigit():
             n += 196 * (int(k[3:]) + 1) * v
         elif k.startswith("wsop") and k[4:].isdigit():
             n += 196 * int(k[4:]) * v
-    return n + 392 * counts.get("sqr", 0) + 30 * counts.get("red", 0) + 222 * counts.get("wred", 0)
+    return (n + 392 * counts.get("sqr", 0) + 30 * counts.get("red", 0) + 222 * counts.get("wred", 0)
+            + 418 * counts.get("sopmw", 0))
 
 
 def write_work_json(outdir):

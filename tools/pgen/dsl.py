@@ -153,7 +153,8 @@ class Prog:
         return v
 
     def _op(self, kind, srcs, u, imm=None, vb=None):
-        half = any(x.half for x in srcs) and kind in ("add", "csub", "getvar")
+        half = any(x.half for x in srcs) and kind in ("add", "csub", "getvar", "swap", "sel", "dppadd", "wxi")
+        assert not half or all(x.half for x in srcs), "%s mixes wide halves and field values" % kind
         v = self._val(u, half, vb) if u else None
         self.cur.items.append(Op(kind, v, list(srcs), imm))
         return v
@@ -265,11 +266,39 @@ class Prog:
         ul = max(-(-c // MASK) for c in climbs)
         return self._op("csub", [a, b], a.u + ul, imm=tuple(climbs))
 
-    def wred(self, lo, hi, u):
+    def wred(self, lo, hi, u, vb=None):
         """Montgomery reduction (lo + hi 2^392) / 2^392 mod q of a wide value;
-        the caller proves the output bound u (checked by evaluate)."""
+        the caller proves the output bound u (checked by evaluate).  The output's
+        limbs are below 2^28 whatever its value (the column pass masks limbs
+        0..12, and the value is below 2^388), so a caller may declare u = 1 with
+        the value bound vb it proves."""
         assert lo.half and hi.half
-        return self._op("wred", [lo, hi], u)
+        return self._op("wred", [lo, hi], u, vb=vb)
+
+    def sopmw(self, a, b, lo, hi, vb):
+        """(a b - W) / 2^392 mod q for a wide value W = lo + hi 2^392 that the
+        caller knows is <= a b as an integer (tower2: the cross term (x + y)^2 -
+        x^2 - y^2 of integer operand sums): the product leaf with limb k of W
+        subtracted in column k (v_mad_i64_i32 by -1, arithmetic carries), then
+        its Montgomery reduction -- a wide product, a wide subtraction and a
+        wred in one pass.  The result is below a b / 2^392 + q; its limbs are
+        below 2^28 (u = 1), vb is the value bound the caller proves."""
+        self._full(a, b)
+        assert lo.half and hi.half
+        assert a.u * b.u <= 8, "sopmw product bound %d*%d (the accumulator has 63 bits)" % (a.u, b.u)
+        assert lo.u <= 7 and hi.u <= 7, "W's limbs must read as signed 32-bit"
+        assert a.vb * b.vb <= VB_PROD, "sopmw value bound %d*%d" % (a.vb, b.vb)
+        return self._op("sopmw", [a, b, lo, hi], 1, vb=vb)
+
+    def wxi(self, a, climbs):
+        """one half of xi times a wide distributed Fq2 value (lane 0: the real
+        coordinate's half, lane 1: the imaginary one's): lane 0 a0 + C - a1,
+        lane 1 a1 + a0, limb-wise -- sel(a, C - a) and the partner add of
+        Tower2.xi as one op.  C (limbs >= a's) is a multiple of q as a wide
+        constant (tower.wide_sub_constant), added on lane 0 only."""
+        assert self.lanes == 2 and a.half
+        ul = max(-(-c // MASK) for c in climbs)
+        return self._op("wxi", [a], a.u + max(ul, a.u), imm=tuple(climbs))
 
     def add(self, a, b):
         return self._op("add", [a, b], a.u + b.u, vb=None if a.half else a.vb + b.vb)
@@ -345,7 +374,8 @@ class Prog:
         """lane r: b + a of lane perm[r] of the pair (one v_add_u32_dpp per limb,
         quad_perm [perm0, perm1, perm0 + 2, perm1 + 2])"""
         assert self.lanes == 2
-        self._full(a, b)
+        if not (a.half and b.half):
+            self._full(a, b)
         return self._cse("dppadd", [a, b], a.u + b.u, imm=tuple(perm), vb=a.vb + b.vb)
 
     def sel(self, a, b):
@@ -670,6 +700,33 @@ def mont_sop_signed(a, b):
     return tuple(gen_fl.limbs(out))
 
 
+def mont_sop_minus_wide(a, b, lo, hi):
+    """exact limbs of emit_sop(minus=...): (s + m q) / R for s = a b - W >= 0,
+    W = lo + hi 2^392, m = -s q^-1 mod R -- every column of the signed 64-bit
+    accumulator checked (limb k of W is subtracted in column k, limb 27 from
+    the top limb at the end)"""
+    cols = [0] * (2 * NL)
+    for i in range(NL):
+        for j in range(NL):
+            cols[i + j] += a[i] * b[j]
+    w = list(lo) + list(hi)
+    s = val_of(a) * val_of(b) - val_of(w)
+    assert s >= 0, "sopmw: the wide value exceeds the product"
+    m = (-s * pow(Q, -1, R)) % R
+    ml = gen_fl.limbs(m)
+    t = s + m * Q
+    assert t % R == 0
+    acc = 0
+    for k in range(2 * NL - 1):
+        acc += cols[k] - w[k] + sum(ml[i] * QL[k - i] for i in range(max(0, k - NL + 1), min(k, NL - 1) + 1))
+        assert -(1 << 63) <= acc < (1 << 63), "sopmw column %d overflows" % k
+        acc >>= 28
+    out = t // R
+    assert 0 <= out < R
+    assert acc - w[2 * NL - 1] == out >> (LB * (NL - 1)), "sopmw top limb"
+    return tuple(gen_fl.limbs(out))
+
+
 def norm_limbs(x):
     """the emitted carry pass: limbs 0..12 below 2^28, the value unchanged"""
     r, c = [], 0
@@ -838,6 +895,8 @@ def evaluate(prog, inputs, stats=None, trace=None):
             return mont_sop([(s[0], s[0])])
         if k == "ssop":
             return mont_sop_signed(s[0], s[1])
+        if k == "sopmw":
+            return mont_sop_minus_wide(s[0], s[1], s[2], s[3])
         if k == "add":
             return tuple(a + b for a, b in zip(*s))
         if k == "add3":
@@ -923,6 +982,10 @@ def evaluate(prog, inputs, stats=None, trace=None):
             return
         elif k == "dppadd":
             r = [tuple(x + y for x, y in zip(s[0][op.imm[ln]], s[1][ln])) for ln in range(L)]
+        elif k == "wxi":
+            assert all(c >= x for c, x in zip(op.imm, s[0][1])), "wxi: constant below the subtrahend limb"
+            r = [tuple(x + c - y for x, c, y in zip(s[0][0], op.imm, s[0][1])),
+                 tuple(x + y for x, y in zip(s[0][1], s[0][0]))]
         elif k in ("wsop", "wnorm"):
             if k == "wsop":
                 st.bump("wsop%d" % (len(op.srcs) // 2))

@@ -479,11 +479,14 @@ class Emitter:
         return k
 
     # ---------------- ops ----------------
-    def emit_sop(self, pairs, d, signed=False):
+    def emit_sop(self, pairs, d, signed=False, minus=None):
         """signed (dsl.Prog._ssop, one pair, b's limbs signed): the products by
         v_mad_i64_i32 into a signed accumulator, arithmetic shifts between
         columns, and the last Montgomery digit + 2^28 (the result + q, so it
-        stays positive); the reduction's products are unsigned either way"""
+        stays positive); the reduction's products are unsigned either way.
+        minus = (lo, hi) (dsl.Prog.sopmw): limb k of that wide value leaves
+        column k (v_mad_i64_i32 by -1; its limb 27 the top limb), the
+        accumulator signed between columns, the total non-negative"""
         first = True
         acc = (ACC, ACC + 1)
         mad = "v_mad_i64_i32" if signed else "v_mad_u64_u32"
@@ -492,6 +495,8 @@ class Emitter:
                 for i in range(max(0, k - NL + 1), min(k, NL - 1) + 1):
                     self.i(mad, ACC, a + i, b + k - i, K(0) if first else ACC)
                     first = False
+            if minus is not None:
+                self.i("v_mad_i64_i32", ACC, (minus[0] + k) if k < NL else (minus[1] + k - NL), K(-1), ACC)
             for i in range(max(0, k - NL + 1), min(k - 1, NL - 1) + 1):
                 self.i("v_mad_u64_u32", ACC, M0 + i, S(SQ + k - i), ACC)
             if k < NL:
@@ -502,8 +507,11 @@ class Emitter:
                 self.i("v_mad_u64_u32", ACC, M0 + k, S(SQ), ACC)
             else:
                 self.i("v_and_b32", d + k - NL, K(MASK), ACC)
-            self.i("v_ashrrev_i64" if signed else "v_lshrrev_b64", ACC, K(28), ACC)
-        self.i("v_mov_b32", d + NL - 1, ACC)
+            self.i("v_ashrrev_i64" if signed or minus is not None else "v_lshrrev_b64", ACC, K(28), ACC)
+        if minus is not None:
+            self.i("v_sub_u32", d + NL - 1, ACC, minus[1] + NL - 1)
+        else:
+            self.i("v_mov_b32", d + NL - 1, ACC)
         del acc
 
     def emit_pdiff(self, a, d):
@@ -696,6 +704,23 @@ class Emitter:
             else:
                 assert n - at[i] - 1 >= 2
                 self.i("v_cndmask_b32_dpp_swap", d + i, d + i, a + i)
+
+    def emit_wxi(self, a, d, c):
+        """d = (a + C - partner's a | a + partner's a) (dsl.Prog.wxi), three
+        instructions per limb: d = C - a; d = VCC ? d : a (VCC = the odd lanes:
+        what the partner needs of this lane); d = a + the partner's d
+        (v_add_u32_dpp).  Limb i's three run in rounds i, i + 1, i + 3, so the
+        DPP read comes more than two wait states after the write and the VOP2
+        cndmasks never follow one another.  d must not alias a."""
+        r = self.ctab_reg(("csub", tuple(c)), c)
+        self.i("s_mov_b64", VCC, S(S_ODD))
+        for n in range(NL + 3):
+            if n < NL:
+                self.i("v_sub_u32", d + n, r(n) if r is not None else K(c[n]), a + n)
+            if 0 <= n - 1 < NL:
+                self.i("v_cndmask_b32", d + n - 1, a + n - 1, d + n - 1)
+            if 0 <= n - 3 < NL:
+                self.i("v_add_u32_dpp", d + n - 3, d + n - 3, a + n - 3, (1, 0))
 
     def emit_sel(self, a, b, d):
         for i in range(NL):
@@ -1250,7 +1275,7 @@ class Emitter:
             # in place over a dying source (safe for every op kind below)
             dk = None
             for vs, kk in zip(srcs, sk):
-                if (vs in dying and self.vslot[kk] is vs and k not in ("swap", "dppadd", "bcast", "pairz", "pdiff")
+                if (vs in dying and self.vslot[kk] is vs and k not in ("swap", "dppadd", "bcast", "pairz", "pdiff", "wxi")
                         and not (k in ("sub", "csub") and op.srcs[0].id == op.srcs[1].id)):
                     dk = kk
                     break
@@ -1279,6 +1304,8 @@ class Emitter:
             self.emit_sop([(base[0], base[0])], d)
         elif k == "ssop":
             self.emit_sop([(base[0], base[1])], d, signed=True)
+        elif k == "sopmw":
+            self.emit_sop([(base[0], base[1])], d, minus=(base[2], base[3]))
         elif k == "pdiff":
             self.emit_pdiff(base[0], d)
         elif k == "red":
@@ -1320,6 +1347,8 @@ class Emitter:
             self.emit_pairz(base[0], d, op.imm)
         elif k == "dppadd":
             self.emit_dppadd(base[0], base[1], d, op.imm)
+        elif k == "wxi":
+            self.emit_wxi(base[0], d, op.imm)
         elif k == "selz":
             nt = op.imm
             self.emit_selz(base[:nt], base[nt], base[nt + 1], d)
@@ -1379,7 +1408,7 @@ class Emitter:
 
     # ---------------- prefetch ----------------
     COST = {"sop": None, "sqr": 460, "red": 62, "norm": 39, "add": 14, "add3": 14, "shladd": 14, "shl": 14, "sub": 28, "neg": 14, "const": 14, "swap": 15,
-            "sel": 14, "dppadd": 15, "bcast": 15, "pairz": 29, "pdiff": 31, "load_raw": 60, "store_raw": 200, "getvar": 0, "setvar": 14, "tload": 7, "tnext": 2,
+            "sel": 14, "dppadd": 15, "bcast": 15, "pairz": 29, "wxi": 43, "pdiff": 31, "load_raw": 60, "store_raw": 200, "getvar": 0, "setvar": 14, "tload": 7, "tnext": 2,
             "selz": 80, "binv": 33000}
     # instructions of other work that hide the load latency (PGEN_AHEAD_L/_M: experiments)
     AHEAD = {"L": int(os.environ.get("PGEN_AHEAD_L", 40)), "M": int(os.environ.get("PGEN_AHEAD_M", 500))}
@@ -1388,6 +1417,8 @@ class Emitter:
     def op_cost(self, op):
         if op.kind == "ssop":
             return 196 * 2 + 71
+        if op.kind == "sopmw":
+            return 196 * 2 + 97
         if op.kind == "sop":
             return 196 * (len(op.srcs) // 2 + 1) + 70
         if op.kind == "wsop":

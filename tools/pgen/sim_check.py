@@ -94,6 +94,10 @@ def check(which, seed=5, lane=3, debug=True):
     print("%s lane %d: %s (%d instructions simulated, %.1fs)" % (which, lane, "OK" if ok else "MISMATCH",
                                                               sm.count, time.time() - t))
     if os.environ.get("PGEN_HIST"):
+        # the two issue classes variants are compared by (profiles/fe2_lazy_sqr/issue_mix.txt)
+        mul = sum(c for m, c in sm.hist.items() if m.startswith("v_mad_") or m == "v_mul_lo_u32")
+        valu = sum(c for m, c in sm.hist.items() if m.startswith("v_"))
+        print("  multiplies (v_mad_*, v_mul_lo_u32) %d, other VALU %d" % (mul, valu - mul))
         for m, c in sorted(sm.hist.items(), key=lambda x: -x[1]):
             print("  %-28s %9d" % (m, c))
     return ok

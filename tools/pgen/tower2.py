@@ -27,6 +27,14 @@ PAIR_DPP = os.environ.get("PGEN_PAIR_DPP", "1") == "1"
 # where carry passes did (FE2 +0.1 % instructions, ML2p -0.14 %); built for
 # A/B as build_gen "ml2ps"
 SQR_SIGNED = os.environ.get("PGEN_SQR_SIGNED", "0") == "1"
+# the Fq4 squarings of the cyclotomic squarings (Granger-Scott fq4_sqr and the
+# halves of Karabina's ksqr) keep their three Fq2 squares double-width and
+# reduce once per output (Tower2.w_sqr2 / w_xi): a one-term wide product is
+# 196 limb MACs and a reduction 222, against 392 per reduced square and a red
+# of each sum.  0: the reduced squares of Tower.fq4_sqr / Tower.ksqr (A/B)
+FE2_LAZY = os.environ.get("PGEN_FE2_LAZY", "1") == "1"
+# within it: (a + b)^2 from the sums of a^2's and b^2's operands (Tower2.w_sqr_pair); 0: from a + b
+SQR_PAIR_SUM = os.environ.get("PGEN_SQR_PAIR_SUM", "1") == "1"
 MUL2_USES = {}       # value id -> mul2 operand uses, from a first build (two_pass)
 MUL2_COUNT = None
 SWAPPED = set()      # value ids whose partner swap a first build formed (outside xi)
@@ -61,7 +69,8 @@ def two_pass(progf, xi_dpp=True):
         finally:
             MUL2_USES, SWAPPED, XI_DPP = {}, set(), True
     return f
-from tower import Tower
+from dsl import Q, VB_PROD
+from tower import KSQR_LAZY_XI, Tower, TowerLazy, Wide, wide_sub_constant
 
 
 class Tower2(Tower):
@@ -187,8 +196,7 @@ class Tower2(Tower):
         ob = p.swap(b)
         return p.sop(x, b, z, ob)     # lane 0: a0 b0 - a1 b1; lane 1: a0 b1 + a1 b0
 
-    def sqr2(self, a):
-        """lane 0: (a0 + a1)(a0 - a1); lane 1: 2 a0 a1"""
+    def _sqr_in(self, a):
         p = self.p
         if a.u > 1:
             # a carry pass (value unchanged) where the product's value bound still
@@ -197,18 +205,112 @@ class Tower2(Tower):
                 a = p.norm_only(a)
             else:
                 a = p.red(a)
-        if SQR_SIGNED:
-            # lane 0: (a1 + a0)(a0 - a1), lane 1: (2 a1) a0; the product adds q
-            # (signed operand), so its value bound is 2
-            x = p.dppadd(a, a, (1, 1))    # a1 + a0 | 2 a1
-            return p.mul(x, p.pdiff(a))
+        return a
+
+    def _sqr_operands(self, a):
+        """(a0 + a1 | 2 a0), (a0 - a1 | a1): the square is their product"""
+        p = self.p
         o = p.swap(a)
         if DPP_ADD:
             x = p.dppadd(a, o, (0, 0))    # o + a0: a0 + a1 | 2 a0, one v_add_u32_dpp per limb
         else:
             x = p.add(o, p.sel(a, o))     # a0 + a1 | 2 a0
         y = p.sel(p.sub(a, o), a)     # a0 - a1 | a1
-        return p.mul(x, y)
+        return x, y
+
+    def sqr2(self, a):
+        """lane 0: (a0 + a1)(a0 - a1); lane 1: 2 a0 a1"""
+        p = self.p
+        a = self._sqr_in(a)
+        if SQR_SIGNED:
+            # lane 0: (a1 + a0)(a0 - a1), lane 1: (2 a1) a0; the product adds q
+            # (signed operand), so its value bound is 2
+            x = p.dppadd(a, a, (1, 1))    # a1 + a0 | 2 a1
+            return p.mul(x, p.pdiff(a))
+        return p.mul(*self._sqr_operands(a))
+
+    # ---------------- lazy Fq4 squaring (FE2_LAZY) ----------------
+    # A wide distributed Fq2 is one tower.Wide: lane 0 holds the real
+    # coordinate's 28 limbs, lane 1 the imaginary one's.  Sums and differences
+    # of squares are lane-local (TowerLazy's half-by-half w_add / w_sub); only
+    # xi mixes the coordinates, one partner exchange per limb (dsl.Prog.wxi).
+    w_sop, w_norm, w_add, w_sub = TowerLazy.w_sop, TowerLazy.w_norm, TowerLazy.w_add, TowerLazy.w_sub
+    _wu = staticmethod(TowerLazy._wu)
+
+    def w_sqr2(self, a):
+        """sqr2 without its reduction"""
+        return self.w_sop(*self._sqr_operands(self._sqr_in(a)))
+
+    def w_sqr_pair(self, a, b):
+        """a^2 and b^2, wide, and a function that gives the reduced cross term
+        (a + b)^2 - a^2 - b^2 when the caller wants it in the op stream.
+        Both operands of a square are linear in its argument, so the third
+        square's operands are the sums of the first two's: two adds and a
+        carry pass (the column bound wants one operand back at limb bound 1)
+        where forming them from a + b takes a carry pass of the sum, the
+        partner swap, its add, a subtraction and a select.  With those integer
+        sums (xa + xb)(ya + yb) >= xa ya + xb yb, so the difference is taken
+        column by column inside the third product's own reduction
+        (dsl.Prog.sopmw) -- no third wide value, no subtraction constant"""
+        p = self.p
+        xa, ya = self._sqr_operands(self._sqr_in(a))
+        xb, yb = self._sqr_operands(self._sqr_in(b))
+        ta, tb = self.w_sop(xa, ya), self.w_sop(xb, yb)
+        xv, yv = xa.vb + xb.vb, ya.vb + yb.vb
+        if SQR_PAIR_SUM and p.use_norm and xa.u + xb.u <= 15 and xv * yv <= VB_PROD and ya.u + yb.u <= 8:
+            def cross():
+                s = self.w_add(ta, tb)
+                if self._wu(s) > 7:
+                    s = self.w_norm(s)
+                bound = (xv * 2 * Q) * (yv * 2 * Q) // (1 << 392) + 1 + Q
+                return p.sopmw(p.norm_only(p.add(xa, xb)), p.add(ya, yb), s.lo, s.hi, -(-bound // (2 * Q)))
+            return ta, tb, cross
+        return ta, tb, lambda: self.w_red(self.w_sub(self.w_sqr2(self.add2(a, b)), self.w_add(ta, tb)))
+
+    def w_xi(self, a):
+        """(a0 - a1, a0 + a1) on a wide value: lane 0 a0 + C - a1, lane 1 a1 + a0"""
+        if self._wu(a) > 3:
+            a = self.w_norm(a)
+        clo, chi, cv = wide_sub_constant(a.lo.u, a.hi.u, a.top)
+        p = self.p
+        return Wide(p.wxi(a.lo, clo), p.wxi(a.hi, chi), a.vb + max(cv, a.vb), a.top + max(chi[13], a.top))
+
+    def w_red(self, a):
+        """one Montgomery reduction of a wide value: (W + m q) / 2^392 < W / 2^392 + q,
+        limbs below 2^28 (dsl.Prog.wred), so u = 1 with that value bound"""
+        bound = a.vb // (1 << 392) + 1 + Q
+        return self.p.wred(a.lo, a.hi, 1, vb=-(-bound // (2 * Q)))
+
+    def fq4_sqr(self, a, b):
+        if not FE2_LAZY:
+            return Tower.fq4_sqr(self, a, b)
+        t = self
+        t0, t1, cross = t.w_sqr_pair(a, b)
+        r0 = t.w_red(t.w_add(t.w_xi(t1), t0))
+        return r0, cross()
+
+    def ksqr(self, g):
+        """Tower.ksqr with each half's x^2 + xi y^2 and 2 x y formed from wide
+        squares, one reduction each; xi on the cross term and the 3 s - 2 z
+        sums after the reduction, as in Tower.ksqr"""
+        if not FE2_LAZY:
+            return Tower.ksqr(self, g)
+        t = self
+        a1, a2, b0, b2 = g
+
+        def half(x, y, z, zy, xi_on_cross):
+            sx, sy, cross = t.w_sqr_pair(x, y)
+            s = t.w_red(t.w_add(sx, t.w_xi(sy)))
+            c = cross()
+            if xi_on_cross:
+                c = t.xi(c) if t.p.use_norm and KSQR_LAZY_XI else t.red2(t.xi(c))
+            nz = t.red2(t.add2(t.dbl2(t.sub2(s, z)), s))
+            nzy = t.red2(t.add2(t.dbl2(t.add2(c, zy)), c))
+            return nz, nzy
+
+        na2, nb0 = half(a1, b2, a2, b0, True)
+        na1, nb2 = half(b0, a2, a1, b2, False)
+        return (na1, na2, nb0, nb2)
 
     def mul_fq(self, a, b):
         return self.p.mul(a, b)       # b replicated

@@ -26,6 +26,31 @@ def dec_prog(lanes=1):
     return p
 
 
+def sqr4_prog(which, lanes=2, raw=None):
+    """the squarings of the final exponentiation's loops on their own
+    (tests/test_pgen_lazy2.py): "fq4": Tower.fq4_sqr of the pairs (a0, b1),
+    (b0, a2), (a1, b2) of an Fq12; "ksqr": Tower.ksqr of its compressed
+    coordinates (a1, a2, b0, b2), the two other Fq2 passed through.
+    raw: a function (prog, k) -> the Fq2 number k of the input as a value of
+    the caller's own bounds instead of a load (the loop-carried state)"""
+    import kernels
+    from tower import Tower
+    from tower2 import Tower2
+    p = Prog("tsqr4%s%d" % (which, lanes), lanes, use_norm=True)
+    T = Tower(p) if lanes == 1 else Tower2(p)
+    V = kernels._Vars(p, lanes)
+    if raw is None:
+        (a0, a1, a2), (b0, b1, b2) = V.load12()
+    else:
+        a0, a1, a2, b0, b1, b2 = (raw(p, k) for k in range(6))
+    if which == "fq4":
+        (a0, b1), (b0, a2), (a1, b2) = T.fq4_sqr(a0, b1), T.fq4_sqr(b0, a2), T.fq4_sqr(a1, b2)
+    else:
+        a1, a2, b0, b2 = T.ksqr((a1, a2, b0, b2))
+    V.store12(((a0, a1, a2), (b0, b1, b2)))
+    return p
+
+
 def unit_prog():
     """binv of a product and of a sum, selz with two tests and with one"""
     p = Prog("tunit", use_norm=True)
