@@ -420,6 +420,59 @@ int pa_fr_legendre_batch(const pa_fr *a, int8_t *out, size_t n);
 /* SqrtField::sqrt fr.rs:592-646 (the reference's Tonelli-Shanks root); ok[i] = 0 (None) for a non-residue */
 int pa_fr_sqrt_batch(const pa_fr *a, pa_fr *out, uint8_t *ok, size_t n);
 
+/* ---- batched Fr NTT: radix-2 evaluation domains ----
+ * For n = 2^log_n: w = ROOT_OF_UNITY^(2^(32 - log_n)) (fr.rs:51-56), g = 7 the
+ * GENERATOR (fr.rs:41-46); rows are Montgomery pa_fr, natural order in and out:
+ *   PA_NTT_FORWARD        out[j] = sum_i in[i] w^(ij)
+ *   PA_NTT_INVERSE        out[j] = n^-1 sum_i in[i] w^(-ij)
+ *   PA_NTT_COSET_FORWARD  forward of in[i] g^i
+ *   PA_NTT_COSET_INVERSE  inverse, then out[i] g^-i
+ * the fft / ifft / coset_fft / icoset_fft of a prover's evaluation domain.
+ * Results are canonical, so they equal any correct transform bit for bit.
+ * `batch` polynomials of n rows each are transformed per call, polynomial b in
+ * rows b n .. b n + n - 1; batch = 0 is a no-op and log_n = 0 the identity.
+ *
+ * A domain owns the power tables of its size on the device that was current
+ * at creation (creation builds them there and waits for that).  log_n up to
+ * PA_NTT_MAX_LOG_N = 28 (pa_fr_ntt_max_log_n()); above it creation returns
+ * PA_ERR_INVALID_ARGUMENT.  The environment variable PA_NTT_TILE_LOG (1..12,
+ * clamped, default 10; a value that is not a number leaves the default) is
+ * read at creation: a transform runs as ceil(log_n / tile_log) passes over HBM,
+ * one launch each.  A pass may have at most 2^24 - 1 workgroups: with the
+ * default tile log (2^11 rows per workgroup) that allows batch * 2^log_n just
+ * under 2^35 rows, with tile logs 1 and 2 (measurement only; as few as 4 and 8
+ * rows per workgroup) 2^26 and 2^27; a larger batch is refused.  The object may be
+ * used from any host thread and lives until pa_fr_ntt_domain_free (NULL is a
+ * no-op); work that reads it must have completed before it is freed.
+ *
+ * in == out (in place) is allowed; with in != out the input is only read.
+ * A NULL domain, an unknown mode, input and output that overlap partly, a
+ * workspace smaller than pa_fr_ntt_workspace_bytes(d, batch) (which is linear
+ * in batch and 0 for a one-pass domain), or a stream on another device than
+ * the domain's return a code before anything is launched.  The workspace must
+ * not overlap in or out.  pa_fr_ntt_device allocates nothing, does not
+ * synchronize, reads nothing back and can be captured into a HIP graph. */
+#define PA_NTT_FORWARD 0
+#define PA_NTT_INVERSE 1
+#define PA_NTT_COSET_FORWARD 2
+#define PA_NTT_COSET_INVERSE 3
+#define PA_NTT_MAX_LOG_N 28
+typedef struct pa_fr_ntt_domain pa_fr_ntt_domain;
+int pa_fr_ntt_domain_create(unsigned log_n, pa_fr_ntt_domain **out);
+void pa_fr_ntt_domain_free(pa_fr_ntt_domain *d);
+unsigned pa_fr_ntt_domain_log_n(const pa_fr_ntt_domain *d);
+size_t pa_fr_ntt_domain_bytes(const pa_fr_ntt_domain *d);   /* device memory it holds */
+unsigned pa_fr_ntt_domain_passes(const pa_fr_ntt_domain *d);     /* launches per transform (0 for log_n = 0) */
+unsigned pa_fr_ntt_domain_tile_log(const pa_fr_ntt_domain *d);   /* PA_NTT_TILE_LOG as clamped */
+/* polynomials that share a workgroup in a one-pass domain (2^11 rows per
+ * workgroup, 2^12 at tile log 12: 2^(11 - log_n)); 0 for a domain of several passes */
+size_t pa_fr_ntt_polys_per_workgroup(const pa_fr_ntt_domain *d);
+unsigned pa_fr_ntt_max_log_n(void);
+size_t pa_fr_ntt_workspace_bytes(const pa_fr_ntt_domain *d, size_t batch);
+int pa_fr_ntt(const pa_fr_ntt_domain *d, int mode, const pa_fr *in, pa_fr *out, size_t batch);   /* host memory */
+int pa_fr_ntt_device(const pa_fr_ntt_domain *d, int mode, const pa_fr *in, pa_fr *out, size_t batch,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- device-resident variants (pointers are device memory) ---- */
 int pa_g1_decode_batch_device(const uint8_t *enc, size_t n, int compressed, int checked, pa_g1_affine *out,
                               uint8_t *status, void *stream);

@@ -614,6 +614,48 @@ private:
     pa_g1_msm_bases* h_ = nullptr;
 };
 
+// A radix-2 evaluation domain of 2^log_n points over Fr (pa_fr_ntt_domain): the
+// fft / ifft / coset_fft / icoset_fft of a prover, over `batch` polynomials laid
+// end to end (rows are Montgomery pa_fr, natural order).  Move-only; the
+// destructor frees the device memory.
+class FrNttDomain {
+public:
+    explicit FrNttDomain(unsigned log_n) { check(pa_fr_ntt_domain_create(log_n, &h_), "FrNttDomain"); }
+    FrNttDomain(const FrNttDomain&) = delete;
+    FrNttDomain& operator=(const FrNttDomain&) = delete;
+    FrNttDomain(FrNttDomain&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    FrNttDomain& operator=(FrNttDomain&& o) noexcept {
+        if (this != &o) {
+            pa_fr_ntt_domain_free(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~FrNttDomain() { pa_fr_ntt_domain_free(h_); }
+
+    unsigned log_n() const { return pa_fr_ntt_domain_log_n(h_); }
+    size_t size() const { return (size_t)1 << log_n(); }
+    const pa_fr_ntt_domain* get() const { return h_; }
+    std::vector<pa_fr> fft(const std::vector<pa_fr>& a) const { return run(PA_NTT_FORWARD, a, "FrNttDomain::fft"); }
+    std::vector<pa_fr> ifft(const std::vector<pa_fr>& a) const { return run(PA_NTT_INVERSE, a, "FrNttDomain::ifft"); }
+    std::vector<pa_fr> coset_fft(const std::vector<pa_fr>& a) const {
+        return run(PA_NTT_COSET_FORWARD, a, "FrNttDomain::coset_fft");
+    }
+    std::vector<pa_fr> icoset_fft(const std::vector<pa_fr>& a) const {
+        return run(PA_NTT_COSET_INVERSE, a, "FrNttDomain::icoset_fft");
+    }
+
+private:
+    std::vector<pa_fr> run(int mode, const std::vector<pa_fr>& a, const char* what) const {
+        if (a.size() % size()) throw std::invalid_argument(std::string(what) + ": rows are not a multiple of the domain");
+        std::vector<pa_fr> out(a.size());
+        if (!a.empty()) check(pa_fr_ntt(h_, mode, a.data(), out.data(), a.size() / size()), what);
+        return out;
+    }
+    pa_fr_ntt_domain* h_ = nullptr;
+};
+
 using G1Uncompressed = Encoded<G1Affine, 1, false>;
 using G1Compressed = Encoded<G1Affine, 1, true>;
 using G2Uncompressed = Encoded<G2Affine, 2, false>;

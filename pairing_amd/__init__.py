@@ -16,8 +16,8 @@ Device-resident entry points for torch tensors live in `pairing_amd.device`.
 """
 import numpy as np
 
-from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, G1MsmBases, PairingError, _lib,
-                      as_rows, call, csr_offsets, device_count, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
+from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, NTT_MAX_LOG_N, FrNttDomain, G1MsmBases,
+                      PairingError, _lib, as_rows, call, csr_offsets, device_count, ntt_mode, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
 
 __all__ = [
     "PairingError", "version", "device_count", "set_device", "set_pairing_kernel", "set_decode_kernel",
@@ -34,6 +34,7 @@ __all__ = [
     "fr_from_repr", "fr_into_repr", "fr_pow", "fr_legendre", "fr_sqrt",
     "g1_affine_mul", "g2_affine_mul", "g1_mul_assign", "g2_mul_assign", "g1_multiexp", "g2_multiexp",
     "G1MsmBases", "g1_msm_prepare", "g1_multiexp_prepared",
+    "FrNttDomain", "fr_ntt_domain", "fr_ntt",
     "g1_eq", "g2_eq", "g1_double", "g2_double", "g1_add", "g2_add", "g1_add_mixed", "g2_add_mixed", "g1_negate", "g2_negate",
     "g1_sub", "g2_sub", "g1_into_affine", "g2_into_affine", "g1_into_projective", "g2_into_projective",
     "g2_batch_normalization", "g2_wnaf_fixed_base",
@@ -628,6 +629,38 @@ def g1_multiexp_prepared(prepared, scalars):
     h = prepared.check_terms(s.shape[0])
     out = np.zeros((1, W_G1), np.uint64)
     call("pa_g1_multiexp_prepared", h, ptr(s), s.shape[0], ptr(out))
+    return out
+
+
+# ---- batched Fr NTT over radix-2 evaluation domains ----
+def fr_ntt_domain(log_n):
+    """The evaluation domain of 2^log_n points on the current device: its power
+    tables are built there once.  Returns an FrNttDomain (log_n, len, close());
+    free it with close() or let it be collected.  PA_NTT_TILE_LOG is read here."""
+    import ctypes
+    log_n = int(log_n)
+    if log_n < 0 or log_n > NTT_MAX_LOG_N:
+        raise ValueError("log_n must be 0..%d, got %d" % (NTT_MAX_LOG_N, log_n))
+    h = ctypes.c_void_p(0)
+    call("pa_fr_ntt_domain_create", log_n, ctypes.byref(h))
+    return FrNttDomain._adopt(h)
+
+
+def fr_ntt(domain, a, mode="forward"):
+    """The domain's transform of each polynomial of `a` ((batch * n, 4) Montgomery
+    Fr rows, polynomial b in rows b n .. b n + n - 1, natural order in and out)
+    as a new array.  mode: "forward" out[j] = sum_i a[i] w^(ij); "inverse" its
+    inverse; "coset_forward" the forward transform of a[i] g^i (g = 7);
+    "coset_inverse" the inverse transform, then out[i] g^-i."""
+    if not isinstance(domain, FrNttDomain):
+        raise ValueError("domain must come from fr_ntt_domain")
+    domain.handle()   # a closed object is rejected first
+    m = ntt_mode(mode)
+    a = as_rows(a, W_FR, "a") if len(a) else np.zeros((0, W_FR), np.uint64)
+    h, batch = domain.check_rows(a.shape[0])
+    out = np.zeros_like(a)
+    if batch:
+        call("pa_fr_ntt", h, m, ptr(a), ptr(out), batch)
     return out
 
 

@@ -156,6 +156,17 @@ _SIGS = {
     "pa_g1_multiexp_prepared_workspace_bytes": [_P, _N],   # returns size_t (below)
     "pa_g1_multiexp_prepared_device": [_P, _P, _N, _P, _P, _N, _P],
     "pa_g1_multiexp_prepared": [_P, _P, _N, _P],
+    "pa_fr_ntt_domain_create": [ctypes.c_uint, ctypes.POINTER(_P)],
+    "pa_fr_ntt_domain_free": [_P],                    # returns nothing (below)
+    "pa_fr_ntt_domain_log_n": [_P],                   # returns unsigned (below)
+    "pa_fr_ntt_domain_bytes": [_P],                   # returns size_t (below)
+    "pa_fr_ntt_domain_passes": [_P],                  # returns unsigned (below)
+    "pa_fr_ntt_domain_tile_log": [_P],                # returns unsigned (below)
+    "pa_fr_ntt_polys_per_workgroup": [_P],            # returns size_t (below)
+    "pa_fr_ntt_max_log_n": [],                        # returns unsigned (below)
+    "pa_fr_ntt_workspace_bytes": [_P, _N],            # returns size_t (below)
+    "pa_fr_ntt": [_P, ctypes.c_int, _P, _P, _N],
+    "pa_fr_ntt_device": [_P, ctypes.c_int, _P, _P, _N, _P, _N, _P],
 }
 for _g in (1, 2):
     for _op in ("double", "negate", "into_affine", "into_projective"):
@@ -208,6 +219,11 @@ _lib.pa_wnaf_exact_workspace_bytes.restype = ctypes.c_size_t
 _lib.pa_g1_msm_bases_len.restype = ctypes.c_size_t
 _lib.pa_g1_multiexp_prepared_workspace_bytes.restype = ctypes.c_size_t
 _lib.pa_multi_pairing_batch_workspace_bytes.restype = ctypes.c_size_t
+_lib.pa_fr_ntt_domain_free.restype = None
+for _name in ("pa_fr_ntt_domain_log_n", "pa_fr_ntt_domain_passes", "pa_fr_ntt_domain_tile_log", "pa_fr_ntt_max_log_n"):
+    getattr(_lib, _name).restype = ctypes.c_uint
+for _name in ("pa_fr_ntt_domain_bytes", "pa_fr_ntt_polys_per_workgroup", "pa_fr_ntt_workspace_bytes"):
+    getattr(_lib, _name).restype = ctypes.c_size_t
 
 
 def version():
@@ -327,6 +343,86 @@ class G1MsmBases:
         h, self._handle = self._handle, None
         if h is not None and self._owns:
             call("pa_g1_msm_bases_free", h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: the library may be gone
+            pass
+
+
+NTT_MODES = {"forward": 0, "inverse": 1, "coset_forward": 2, "coset_inverse": 3}   # PA_NTT_* of the header
+NTT_MAX_LOG_N = int(_lib.pa_fr_ntt_max_log_n())
+
+
+def ntt_mode(mode):
+    """the PA_NTT_* code of a mode name; anything else is a ValueError"""
+    try:
+        return NTT_MODES[mode]
+    except (KeyError, TypeError):
+        raise ValueError("mode must be one of %s, got %r" % (", ".join(NTT_MODES), mode)) from None
+
+
+class FrNttDomain:
+    """A pa_fr_ntt_domain handle: the power tables of one radix-2 evaluation
+    domain of 2^log_n points on one device (include/pairing_amd.h).  `log_n`,
+    `len` = 2^log_n, `passes`, `tile_log`, `polys_per_workgroup`, `bytes` (device
+    memory held) are read at creation;
+    close() frees the device memory, is idempotent and also runs when the
+    object is collected.  Any use after close() raises ValueError before a
+    native call.  owns=False wraps a handle someone else frees."""
+
+    def __init__(self, handle, log_n, owns=True, passes=0, tile_log=0, polys_per_workgroup=0, nbytes=0):
+        self._handle = handle
+        self._owns = owns
+        self.log_n = int(log_n)
+        self.len = 1 << self.log_n
+        self.passes = int(passes)
+        self.tile_log = int(tile_log)
+        self.polys_per_workgroup = int(polys_per_workgroup)
+        self.bytes = int(nbytes)
+
+    @classmethod
+    def _adopt(cls, handle):
+        """take ownership of a handle pa_fr_ntt_domain_create just returned"""
+        h = ctypes.c_void_p(handle.value)
+        return cls(h, _lib.pa_fr_ntt_domain_log_n(h),
+                   passes=_lib.pa_fr_ntt_domain_passes(h), tile_log=_lib.pa_fr_ntt_domain_tile_log(h),
+                   polys_per_workgroup=_lib.pa_fr_ntt_polys_per_workgroup(h), nbytes=_lib.pa_fr_ntt_domain_bytes(h))
+
+    def __len__(self):
+        return self.len
+
+    @property
+    def closed(self):
+        return self._handle is None
+
+    def handle(self):
+        if self._handle is None:
+            raise ValueError("NTT domain used after close()")
+        return self._handle
+
+    def check_rows(self, rows):
+        """(handle, batch) after checking that `rows` is a positive multiple of 2^log_n, or zero rows"""
+        h = self.handle()
+        if rows % self.len:
+            raise ValueError("%d rows are not a multiple of the domain's %d points" % (rows, self.len))
+        return h, rows // self.len
+
+    def workspace_bytes(self, batch):
+        """pa_fr_ntt_workspace_bytes(domain, batch): 0 for a one-pass domain"""
+        return int(_lib.pa_fr_ntt_workspace_bytes(self.handle(), int(batch)))
+
+    def close(self):
+        h, self._handle = self._handle, None
+        if h is not None and self._owns:
+            _lib.pa_fr_ntt_domain_free(h)
 
     def __enter__(self):
         return self

@@ -1696,6 +1696,103 @@ int pa_g1_multiexp_prepared(const pa_g1_msm_bases* b, const pa_fr_repr* scalars,
     return download(out, dout, sizeof(pa_g1));
 }
 
+// ---- batched Fr NTT over a radix-2 evaluation domain (kernels_ntt.hip) ----
+// The object owns the power tables of its size on one device; the tile log
+// (PA_NTT_TILE_LOG) is read when it is created and fixes the pass structure.
+struct pa_fr_ntt_domain {
+    int dev = 0;
+    pa::NttLayout layout{};
+    uint64_t* tables = nullptr;
+};
+
+int pa_fr_ntt_domain_create(unsigned log_n, pa_fr_ntt_domain** out) {
+    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    *out = nullptr;
+    if (log_n > pa::kNttMaxLogN) return fail(PA_ERR_INVALID_ARGUMENT, "NTT domains support log_n <= 28");
+    unsigned tile_log = pa::kNttDefaultTileLog;
+    if (const char* e = getenv("PA_NTT_TILE_LOG")) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end != e && *end == '\0')   // anything that is not a number leaves the default
+            tile_log = v < 1 ? 1u : (v > (long)pa::kNttMaxTileLog ? pa::kNttMaxTileLog : (unsigned)v);
+    }
+    pa_fr_ntt_domain* d = new pa_fr_ntt_domain;
+    d->layout = pa::ntt_layout(log_n, tile_log);
+    hipError_t e = hipGetDevice(&d->dev);
+    if (e == hipSuccess) e = hipMalloc((void**)&d->tables, d->layout.rows * 32);
+    if (e == hipSuccess) e = pa::launch_ntt_build(d->layout, d->tables, call_stream());
+    if (e == hipSuccess) e = call_sync();
+    if (e != hipSuccess) {
+        if (d->tables) (void)hipFree(d->tables);
+        delete d;
+        return fail(hip_code(e), "create NTT domain", e);
+    }
+    *out = d;
+    return PA_OK;
+}
+void pa_fr_ntt_domain_free(pa_fr_ntt_domain* d) {
+    if (!d) return;
+    if (d->tables) (void)hipFree(d->tables);
+    delete d;
+}
+unsigned pa_fr_ntt_domain_log_n(const pa_fr_ntt_domain* d) { return d ? d->layout.log_n : 0; }
+size_t pa_fr_ntt_domain_bytes(const pa_fr_ntt_domain* d) { return d ? d->layout.rows * 32 : 0; }
+unsigned pa_fr_ntt_domain_passes(const pa_fr_ntt_domain* d) { return d ? d->layout.passes : 0; }
+unsigned pa_fr_ntt_domain_tile_log(const pa_fr_ntt_domain* d) { return d ? d->layout.tile_log : 0; }
+size_t pa_fr_ntt_polys_per_workgroup(const pa_fr_ntt_domain* d) {
+    return d ? pa::ntt_polys_per_workgroup(d->layout) : 0;
+}
+unsigned pa_fr_ntt_max_log_n(void) { return pa::kNttMaxLogN; }
+size_t pa_fr_ntt_workspace_bytes(const pa_fr_ntt_domain* d, size_t batch) {
+    return d && pa::ntt_batch_fits(d->layout, batch) ? pa::ntt_workspace_bytes(d->layout, batch) : 0;
+}
+
+namespace {
+// the checks of both transform entries; `in` / `out` are only compared
+int ntt_check(const pa_fr_ntt_domain* d, int mode, const pa_fr* in, pa_fr* out, size_t batch) {
+    if (!d) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (mode < PA_NTT_FORWARD || mode > PA_NTT_COSET_INVERSE) return fail(PA_ERR_INVALID_ARGUMENT, "unknown NTT mode");
+    if (batch == 0) return PA_OK;
+    if (!in || !out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!pa::ntt_batch_fits(d->layout, batch))
+        return fail(PA_ERR_INVALID_ARGUMENT, "NTT batch too large (a pass of the domain's tile log would exceed a grid)");
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+    const size_t bytes = (batch << d->layout.log_n) * sizeof(pa_fr);
+    if (a != b && a < b + bytes && b < a + bytes)
+        return fail(PA_ERR_INVALID_ARGUMENT, "NTT input and output overlap partially");
+    return PA_OK;
+}
+}  // namespace
+
+int pa_fr_ntt_device(const pa_fr_ntt_domain* d, int mode, const pa_fr* in, pa_fr* out, size_t batch, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (int rc = ntt_check(d, mode, in, out, batch)) return rc;
+    if (batch == 0) return PA_OK;
+    const size_t need = pa::ntt_workspace_bytes(d->layout, batch);
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_fr_ntt_workspace_bytes");
+    int dev = 0;
+    PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
+    if (dev != d->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the NTT domain");
+    PA_TRY(pa::launch_ntt(d->layout, d->tables, mode, (const uint64_t*)in, (uint64_t*)out, batch, workspace,
+                          (hipStream_t)stream),
+           "kernel launch");
+    return PA_OK;
+}
+int pa_fr_ntt(const pa_fr_ntt_domain* d, int mode, const pa_fr* in, pa_fr* out, size_t batch) {
+    if (int rc = ntt_check(d, mode, in, out, batch)) return rc;
+    if (batch == 0) return PA_OK;
+    DevBuf da, dws;
+    int rc;
+    const size_t bytes = (batch << d->layout.log_n) * sizeof(pa_fr);
+    if ((rc = upload(da, in, bytes))) return rc;
+    const size_t ws = pa::ntt_workspace_bytes(d->layout, batch);
+    PA_TRY(dws.alloc(ws), "device scratch");
+    if ((rc = pa_fr_ntt_device(d, mode, da.as<pa_fr>(), da.as<pa_fr>(), batch, dws.p, ws, call_stream()))) return rc;
+    PA_TRY(call_sync(), "kernel execution");
+    return download(out, da, bytes);
+}
+
 // ---- CurveProjective / CurveAffine surface, G1 and G2 (kernels_group.hip) ----
 namespace {
 constexpr size_t jac_bytes(int group) { return group == 1 ? sizeof(pa_g1) : sizeof(pa_g2); }

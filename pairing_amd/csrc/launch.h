@@ -213,6 +213,37 @@ hipError_t launch_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* 
                         const uint64_t* exp, int exp_words, size_t n, hipStream_t stream);
 hipError_t launch_fr_mul_batch(const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, hipStream_t stream);
 
+// ---- batched Fr NTT over radix-2 evaluation domains (kernels_ntt.hip) ----
+constexpr unsigned kNttMaxLogN = 28;       // 2^28 rows of 32 B = 8 GiB per polynomial
+constexpr unsigned kNttGroupLog = 11;      // rows a workgroup holds in LDS: 2^11 x 32 B = 64 KiB (2^12 at tile log 12)
+constexpr unsigned kNttMaxTileLog = 12;    // butterfly stages per pass at most: 128 KiB of LDS, one workgroup per CU
+constexpr unsigned kNttDefaultTileLog = 10;
+constexpr unsigned kNttSplitLog = 12;      // two-level power tables: w^e = lo[e mod 2^12] * hi[e >> 12]
+enum NttMode : int { NTT_FORWARD = 0, NTT_INVERSE, NTT_COSET_FORWARD, NTT_COSET_INVERSE };
+// What a domain holds on the device, as offsets in 32-byte rows into one
+// allocation: for each direction the in-tile twiddles w_T^m (m < T/2, T the
+// largest tile), the two-level tables of w_n and of the coset generator, and
+// n^-1 (folded into the inverse generator's low table as well).
+struct NttLayout {
+    unsigned log_n, tile_log, split_log, passes;
+    size_t tile_rows, lo_rows, hi_rows;      // table lengths
+    size_t tile[2], lo[2], hi[2], glo[2], ghi[2], ninv;   // [0] forward, [1] inverse
+    size_t rows;                             // total
+};
+NttLayout ntt_layout(unsigned log_n, unsigned tile_log);
+// log2 of the rows a workgroup holds
+inline unsigned ntt_group_log(const NttLayout& l) { return l.tile_log > kNttGroupLog ? l.tile_log : kNttGroupLog; }
+// polynomials that share a workgroup when the transform is one launch (0 for several passes)
+size_t ntt_polys_per_workgroup(const NttLayout& l);
+size_t ntt_workspace_bytes(const NttLayout& l, size_t batch);
+// false if a pass would need more workgroups than a grid holds
+bool ntt_batch_fits(const NttLayout& l, size_t batch);
+hipError_t launch_ntt_build(const NttLayout& l, uint64_t* tables, hipStream_t stream);
+// in == out allowed; with more than one pass the passes go in -> workspace
+// (in place there) -> out, so `in` is only read
+hipError_t launch_ntt(const NttLayout& l, const uint64_t* tables, int mode, const uint64_t* in, uint64_t* out,
+                      size_t batch, void* workspace, hipStream_t stream);
+
 // ---- bit-exact Wnaf (kernels_wnaf_exact.hip) ----
 constexpr int kWxMaxWindow = 20;         // fixed base: 2^19 table entries, int32 digits
 constexpr int kWxMaxScalarWindow = 12;   // fixed scalar: a table per base

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, G1MsmBases, _lib, call, csr_offsets
+from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, FrNttDomain, G1MsmBases, _lib, call, csr_offsets, ntt_mode
 
 
 def _stream_ptr(stream):
@@ -308,6 +308,31 @@ def fr_mul(a, b, out, stream=None):
     _rows(b, a.shape[0], "b")
     _rows(out, a.shape[0], "out")
     call("pa_fr_mul_batch_device", *args, a.shape[0], _stream_ptr(stream))
+
+
+def fr_ntt_workspace_words(domain, batch):
+    """int64 words of `workspace` for fr_ntt over `batch` polynomials (0 for a one-pass domain)."""
+    return (domain.workspace_bytes(batch) + 7) // 8
+
+
+def fr_ntt(domain, a, out, mode, workspace=None, stream=None):
+    """The domain's transform of the batch * n Montgomery Fr rows of `a` into the same
+    rows of `out` ((rows, 4) int64, natural order; out may be a itself, and rows of
+    out past the batch are left alone).  mode "forward", "inverse", "coset_forward"
+    or "coset_inverse"; workspace: an int64 buffer of fr_ntt_workspace_words(domain,
+    batch), not needed where that is 0.  Nothing is allocated or read back."""
+    if not isinstance(domain, FrNttDomain):
+        raise ValueError("domain must come from fr_ntt_domain")
+    domain.handle()   # a closed object is rejected first
+    m = ntt_mode(mode)
+    h, batch = domain.check_rows(a.shape[0])
+    _rows(out, a.shape[0], "out")
+    need = fr_ntt_workspace_words(domain, batch)
+    if need and workspace is None:
+        raise ValueError("workspace must be a contiguous int64 CUDA tensor of >= %d words" % need)
+    ws = _words(workspace, need, "workspace") if need else ctypes.c_void_p(0)
+    args = (_dptr(a, 4, "a"), _dptr(out, 4, "out"))
+    call("pa_fr_ntt_device", h, m, *args, batch, ws, need * 8, _stream_ptr(stream))
 
 
 def multiexp_workspace(group, n, device):
