@@ -396,6 +396,32 @@ size_t pa_g1_multiexp_prepared_workspace_bytes(const pa_g1_msm_bases *bases, siz
 int pa_g1_multiexp_prepared_device(const pa_g1_msm_bases *bases, const pa_fr_repr *dev_scalars, size_t m,
                                    pa_g1 *dev_out, void *workspace, size_t workspace_bytes, void *stream);
 int pa_g1_multiexp_prepared(const pa_g1_msm_bases *bases, const pa_fr_repr *host_scalars, size_t m, pa_g1 *out);
+/* A batch of k scalar vectors over the same prepared bases, in one pipeline:
+ *   out[j] = sum_{i < m} s[j * m + i] * P_i   for j < k,
+ * the vectors end to end (the layout of pa_fr_ntt's `batch` polynomials), each
+ * result equal as a point to pa_g1_multiexp_prepared over that vector.  k = 0
+ * writes nothing and returns PA_OK; m = 0 writes k zero points.  k = 1 with
+ * PA_MSM_SCALARS_REPR runs the job of pa_g1_multiexp_prepared_device.
+ * flags: PA_MSM_SCALARS_REPR, rows are pa_fr_repr (any 256-bit value), or
+ * PA_MSM_SCALARS_MONTGOMERY, rows are pa_fr (Montgomery, what pa_fr_ntt
+ * writes) and are taken through into_repr on the device; in that mode the
+ * result for a row that is not below r is unspecified.
+ * Item positions and bucket keys are 32-bit.  With W windows of c bits and B =
+ * 2^(c-1) buckets per window over nt terms (2m and 130 bits when the bases are
+ * in the subgroup, else m and 257 bits), a batch is valid while k * W * nt <=
+ * 2^32 - 1 and k * W * B < 2^32.  Beyond that ..._workspace_bytes returns 0
+ * and the entries return PA_ERR_INVALID_ARGUMENT; the caller splits the batch.
+ * Errors (m > len, unknown flag bits, a batch over the limit, a workspace
+ * smaller than ..._batch_workspace_bytes(bases, m, k), a stream on another
+ * device than the object's) return a code before anything is launched. */
+#define PA_MSM_SCALARS_REPR        0u
+#define PA_MSM_SCALARS_MONTGOMERY  1u
+size_t pa_g1_multiexp_prepared_batch_workspace_bytes(const pa_g1_msm_bases *bases, size_t m, size_t k);
+int pa_g1_multiexp_prepared_batch_device(const pa_g1_msm_bases *bases, const void *dev_scalars, size_t m, size_t k,
+                                         unsigned flags, pa_g1 *dev_out, void *workspace, size_t workspace_bytes,
+                                         void *stream);
+int pa_g1_multiexp_prepared_batch(const pa_g1_msm_bases *bases, const void *host_scalars, size_t m, size_t k,
+                                  unsigned flags, pa_g1 *out);
 
 /* ---- scalar field Fr (src/bls12_381/fr.rs; SURVEY.md §8 f, rank 4) ----
  * pa_fr = 4 x u64 LE limbs, Montgomery form with R = 2^256, < r: the

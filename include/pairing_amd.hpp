@@ -609,8 +609,26 @@ public:
         check(pa_g1_multiexp_prepared(h_, s.empty() ? nullptr : &s[0].v, s.size(), &r.v), "G1MsmBases::multiexp");
         return r;
     }
+    // k vectors of s.size() / k scalars end to end, one pipeline: result j is
+    // sum_i s[j m + i] * bases_i, the same point as multiexp over that vector
+    std::vector<G1> multiexp_batch(const std::vector<FrRepr>& s, size_t k) const {
+        static_assert(sizeof(FrRepr) == sizeof(pa_fr_repr), "FrRepr rows are pa_fr_repr rows");
+        return batch(s.empty() ? nullptr : &s[0].v, s.size(), k, PA_MSM_SCALARS_REPR);
+    }
+    // ... over Montgomery rows below r (what FrNttDomain's transforms return)
+    std::vector<G1> multiexp_batch(const std::vector<pa_fr>& s, size_t k) const {
+        return batch(s.data(), s.size(), k, PA_MSM_SCALARS_MONTGOMERY);
+    }
 
 private:
+    std::vector<G1> batch(const void* s, size_t rows, size_t k, unsigned flags) const {
+        if (k ? rows % k != 0 : rows != 0)
+            throw std::invalid_argument("G1MsmBases::multiexp_batch: rows are not k vectors of equal length");
+        static_assert(sizeof(G1) == sizeof(pa_g1), "G1 rows are pa_g1 rows");
+        std::vector<G1> r(k);
+        if (k) check(pa_g1_multiexp_prepared_batch(h_, s, rows / k, k, flags, &r[0].v), "G1MsmBases::multiexp_batch");
+        return r;
+    }
     pa_g1_msm_bases* h_ = nullptr;
 };
 

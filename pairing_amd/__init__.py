@@ -17,7 +17,7 @@ Device-resident entry points for torch tensors live in `pairing_amd.device`.
 import numpy as np
 
 from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, NTT_MAX_LOG_N, FrNttDomain, G1MsmBases,
-                      PairingError, _lib, as_rows, call, csr_offsets, device_count, ntt_mode, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
+                      PairingError, _lib, as_rows, batch_shape, call, csr_offsets, device_count, msm_scalars, ntt_mode, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
 
 __all__ = [
     "PairingError", "version", "device_count", "set_device", "set_pairing_kernel", "set_decode_kernel",
@@ -33,7 +33,7 @@ __all__ = [
     "fr_mul", "fr_square", "fr_add", "fr_sub", "fr_double", "fr_negate", "fr_inverse",
     "fr_from_repr", "fr_into_repr", "fr_pow", "fr_legendre", "fr_sqrt",
     "g1_affine_mul", "g2_affine_mul", "g1_mul_assign", "g2_mul_assign", "g1_multiexp", "g2_multiexp",
-    "G1MsmBases", "g1_msm_prepare", "g1_multiexp_prepared",
+    "G1MsmBases", "g1_msm_prepare", "g1_multiexp_prepared", "g1_multiexp_prepared_batch",
     "FrNttDomain", "fr_ntt_domain", "fr_ntt",
     "g1_eq", "g2_eq", "g1_double", "g2_double", "g1_add", "g2_add", "g1_add_mixed", "g2_add_mixed", "g1_negate", "g2_negate",
     "g1_sub", "g2_sub", "g1_into_affine", "g2_into_affine", "g1_into_projective", "g2_into_projective",
@@ -629,6 +629,23 @@ def g1_multiexp_prepared(prepared, scalars):
     h = prepared.check_terms(s.shape[0])
     out = np.zeros((1, W_G1), np.uint64)
     call("pa_g1_multiexp_prepared", h, ptr(s), s.shape[0], ptr(out))
+    return out
+
+
+def g1_multiexp_prepared_batch(prepared, scalars, count=None, montgomery=False):
+    """k multiexps over the same prepared bases in one call: scalars (k, m, 4), or
+    (k * m, 4) rows with count=k vectors end to end; row j of the (k, 18) result is
+    sum_i s[j][i] * P_i over the first m prepared bases, the same point as
+    g1_multiexp_prepared(prepared, s[j]).  The rows are FrRepr (any 256-bit value),
+    or with montgomery=True Montgomery Fr below r (what fr_ntt returns)."""
+    if not isinstance(prepared, G1MsmBases):
+        raise ValueError("prepared must come from g1_msm_prepare")
+    prepared.handle()   # a closed object is rejected first
+    flags = msm_scalars(montgomery)
+    s, k, m = batch_shape(scalars, count)
+    h = prepared.check_terms(m)
+    out = np.zeros((k, W_G1), np.uint64)
+    call("pa_g1_multiexp_prepared_batch", h, ptr(s), m, k, flags, ptr(out))
     return out
 
 

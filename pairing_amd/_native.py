@@ -156,6 +156,9 @@ _SIGS = {
     "pa_g1_multiexp_prepared_workspace_bytes": [_P, _N],   # returns size_t (below)
     "pa_g1_multiexp_prepared_device": [_P, _P, _N, _P, _P, _N, _P],
     "pa_g1_multiexp_prepared": [_P, _P, _N, _P],
+    "pa_g1_multiexp_prepared_batch_workspace_bytes": [_P, _N, _N],   # returns size_t (below)
+    "pa_g1_multiexp_prepared_batch_device": [_P, _P, _N, _N, ctypes.c_uint, _P, _P, _N, _P],
+    "pa_g1_multiexp_prepared_batch": [_P, _P, _N, _N, ctypes.c_uint, _P],
     "pa_fr_ntt_domain_create": [ctypes.c_uint, ctypes.POINTER(_P)],
     "pa_fr_ntt_domain_free": [_P],                    # returns nothing (below)
     "pa_fr_ntt_domain_log_n": [_P],                   # returns unsigned (below)
@@ -218,6 +221,7 @@ _lib.pa_wnaf_exact_workspace_bytes.argtypes = [ctypes.c_int, _N, ctypes.c_int, c
 _lib.pa_wnaf_exact_workspace_bytes.restype = ctypes.c_size_t
 _lib.pa_g1_msm_bases_len.restype = ctypes.c_size_t
 _lib.pa_g1_multiexp_prepared_workspace_bytes.restype = ctypes.c_size_t
+_lib.pa_g1_multiexp_prepared_batch_workspace_bytes.restype = ctypes.c_size_t
 _lib.pa_multi_pairing_batch_workspace_bytes.restype = ctypes.c_size_t
 _lib.pa_fr_ntt_domain_free.restype = None
 for _name in ("pa_fr_ntt_domain_log_n", "pa_fr_ntt_domain_passes", "pa_fr_ntt_domain_tile_log", "pa_fr_ntt_max_log_n"):
@@ -355,6 +359,33 @@ class G1MsmBases:
             self.close()
         except Exception:   # interpreter shutdown: the library may be gone
             pass
+
+
+MSM_SCALARS_REPR, MSM_SCALARS_MONTGOMERY = 0, 1   # PA_MSM_SCALARS_* of the header
+
+
+def msm_scalars(montgomery):
+    """the PA_MSM_SCALARS_* flag of a batched multiexp: False for FrRepr rows,
+    True for Montgomery Fr rows; anything else is a ValueError"""
+    if montgomery is True or montgomery is False:
+        return MSM_SCALARS_MONTGOMERY if montgomery else MSM_SCALARS_REPR
+    raise ValueError("montgomery must be True or False, got %r" % (montgomery,))
+
+
+def batch_shape(scalars, count, name="scalars"):
+    """(rows, k, m) of a batched multiexp's scalars: a (k, m, 4) array, or
+    (k * m, 4) rows with count = k vectors end to end"""
+    a = np.ascontiguousarray(scalars, dtype=np.uint64)
+    if a.ndim == 3 and count is None:
+        if a.shape[2] != 4:
+            raise ValueError("%s must have shape (k, m, 4), got %s" % (name, a.shape))
+        return a.reshape(-1, 4), a.shape[0], a.shape[1]
+    if a.ndim != 2 or a.shape[1] != 4 or count is None:
+        raise ValueError("%s must have shape (k, m, 4), or (k * m, 4) with count=k, got %s" % (name, a.shape))
+    k = int(count)
+    if k < 0 or (k == 0 and a.shape[0]) or (k and a.shape[0] % k):
+        raise ValueError("%d rows of %s are not %d vectors of equal length" % (a.shape[0], name, k))
+    return a, k, a.shape[0] // k if k else 0
 
 
 NTT_MODES = {"forward": 0, "inverse": 1, "coset_forward": 2, "coset_inverse": 3}   # PA_NTT_* of the header

@@ -1696,6 +1696,60 @@ int pa_g1_multiexp_prepared(const pa_g1_msm_bases* b, const pa_fr_repr* scalars,
     return download(out, dout, sizeof(pa_g1));
 }
 
+// k scalar vectors over the same prepared bases in one pipeline
+namespace {
+// what both batch entries refuse before touching memory; 0 = go on
+int batch_args(const pa_g1_msm_bases* b, size_t m, size_t k, unsigned flags) {
+    if (flags & ~PA_MSM_SCALARS_MONTGOMERY) return fail(PA_ERR_INVALID_ARGUMENT, "unknown PA_MSM_SCALARS_* flag bits");
+    if (m > b->n) return fail(PA_ERR_INVALID_ARGUMENT, "more scalars than prepared bases");
+    if (!pa::msm_prepared_batch_fits(m, k, b->in_subgroup != 0))
+        return fail(PA_ERR_INVALID_ARGUMENT,
+                    "batch over the 32-bit item limit (k * windows * terms <= 2^32 - 1, k * windows * buckets < 2^32): "
+                    "split it");
+    return PA_OK;
+}
+}  // namespace
+size_t pa_g1_multiexp_prepared_batch_workspace_bytes(const pa_g1_msm_bases* b, size_t m, size_t k) {
+    return b && m <= b->n ? pa::msm_prepared_batch_workspace_bytes(m, k, b->in_subgroup != 0) : 0;
+}
+int pa_g1_multiexp_prepared_batch_device(const pa_g1_msm_bases* b, const void* scalars, size_t m, size_t k,
+                                         unsigned flags, pa_g1* out, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+    if (!b) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    int rc;
+    if ((rc = batch_args(b, m, k, flags))) return rc;
+    if (k == 0) return PA_OK;
+    if (!out || (m && (!scalars || !workspace))) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (m && workspace_bytes < pa::msm_prepared_batch_workspace_bytes(m, k, b->in_subgroup != 0))
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_g1_multiexp_prepared_batch_workspace_bytes");
+    int dev = 0;
+    PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
+    if (dev != b->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the prepared bases");
+    PA_TRY(pa::launch_msm_prepared_g1_batch(b->rows, b->n, b->in_subgroup != 0, (const uint64_t*)scalars, m, k,
+                                            (flags & PA_MSM_SCALARS_MONTGOMERY) != 0, (uint64_t*)out, workspace,
+                                            workspace_bytes, (hipStream_t)stream),
+           "kernel launch");
+    return PA_OK;
+}
+int pa_g1_multiexp_prepared_batch(const pa_g1_msm_bases* b, const void* scalars, size_t m, size_t k, unsigned flags,
+                                  pa_g1* out) {
+    if (!b) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    int rc;
+    if ((rc = batch_args(b, m, k, flags))) return rc;
+    if (k == 0) return PA_OK;
+    if (!out || (m && !scalars)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    DevBuf ds, dout, dws;
+    // k m rows fit: a batch within the item limit has k * m < 2^32
+    if ((rc = upload(ds, scalars, sizeof(pa_fr_repr) * m * k))) return rc;
+    PA_TRY(dout.alloc(sizeof(pa_g1) * k), "device scratch");
+    const size_t ws = pa::msm_prepared_batch_workspace_bytes(m, k, b->in_subgroup != 0);
+    PA_TRY(dws.alloc(ws), "device scratch");
+    if ((rc = pa_g1_multiexp_prepared_batch_device(b, ds.p, m, k, flags, dout.as<pa_g1>(), dws.p, ws, call_stream())))
+        return rc;
+    PA_TRY(call_sync(), "kernel execution");
+    return download(out, dout, sizeof(pa_g1) * k);
+}
+
 // ---- batched Fr NTT over a radix-2 evaluation domain (kernels_ntt.hip) ----
 // The object owns the power tables of its size on one device; the tile log
 // (PA_NTT_TILE_LOG) is read when it is created and fixes the pass structure.

@@ -43,12 +43,19 @@
 // below 2^129, and steps 2-7 run over 2m virtual terms and ceil(130 / c)
 // windows: the same msm_run with another digit kernel, term count and window
 // count (MsmJob).  Otherwise the 257-bit pipeline runs over rows [0, m).
+//
+// A batch of k scalar vectors over the same prepared bases
+// (launch_msm_prepared_g1_batch) is the same pipeline over k W windows: vector
+// j's window w is window j W + w, its items gather the same rows, the window
+// parts are ranges of vectors and k_msm_horner_batch_q runs every vector's
+// Horner chain side by side.  The digit kernels take Montgomery Fr rows too.
 
 #include <vector>
 
 #include "curve_fl.h"
 #include "curve_fl2.h"
 #include "dec_quad.h"
+#include "fr.h"
 #include "glv_split.h"
 #include "launch_msm.h"
 
@@ -121,9 +128,12 @@ struct MsmPlan {
     uint32_t passes;            // counting-sort passes over the c-1 magnitude bits
     uint32_t T;                 // items per lane of the bucket accumulation
     uint32_t tpw;               // sort tiles per window
-    size_t items;               // W * nt
+    size_t k;                   // scalar vectors (a batch: window j W + w is vector j's window w)
+    size_t WT;                  // k * W windows in all
+    bool fits;                  // 32-bit item positions and keys: WT n <= 2^32 - 1 and WT B < 2^32
+    size_t items;               // WT * nt
     size_t off_keys_in, off_keys_out, off_vals_in, off_vals_out, off_start, off_end;
-    size_t off_buckets, off_segs, off_tmp, off_hist, off_wtot, off_cont, off_basefl, off_hacc, off_long;
+    size_t off_buckets, off_segs, off_tmp, off_hist, off_wtot, off_cont, off_basefl, off_hacc, off_long, off_wpre;
     size_t total;
 };
 
@@ -162,6 +172,24 @@ static inline uint32_t msm_window_bits_glv(size_t nt) {
     if (lg >= 20) return 15;
     const int c = lg - 3;
     return (uint32_t)(c < 4 ? 4 : (c > 13 ? 13 : c));
+}
+
+// A batch's window bits (PA_MSM_BATCH_C to A/B an absolute value).  The
+// bucket reduction of k W windows is throughput work beside the k W nt mixed
+// additions, which moves the optimum little: the single call's rule measured
+// within its neighbours' spread at the batch shapes (profiles/msm_prepared_batch/):
+// 16 vectors of 2^16 terms, c = 11 / 12 / 13 / 14 / 15: 7.92 / 7.81 / 8.01 /
+// 9.17 / 10.38 ms (64 vectors: 26.3 / 25.5 / 25.6 / 29.1 / 33.3); 256 vectors of
+// 2^12 terms, c = 8 / 9 / 10 / 11: 12.4 / 11.1 / 11.3 / 10.6 ms; 8 vectors of
+// 2^18 terms, c = 12 / 13 / 14 / 15: 12.6 / 11.8 / 11.7 / 13.0 ms.  So the rule
+// is the single call's, which also makes a batch of one vector its job.
+static inline uint32_t msm_window_bits_batch(size_t nt) {
+    static const int env = [] {
+        const char* v = getenv("PA_MSM_BATCH_C");
+        const int k = v ? atoi(v) : 0;
+        return k < 4 || k > 20 ? 0 : k;
+    }();
+    return env ? (uint32_t)env : msm_window_bits_glv(nt);
 }
 
 // items (sorted (bucket, term) pairs) per lane of the bucket accumulation
@@ -228,13 +256,34 @@ static uint32_t msm_parts(uint32_t W) {
     return parts < W ? parts : W;
 }
 
+// A batch's parts are ranges of vectors (PA_MSM_BATCH_PARTS to A/B, default 1).
+// A single MSM hides its upper parts' latency-bound tails under the next part's
+// accumulation; a batch's reduction and Horner grid are wide enough to fill
+// the chip themselves, and on side streams they only compete with the
+// accumulation: 1 / 2 / 4 / 8 parts measured 7.45 / 8.01 / 9.42 / 10.81 ms at
+// 16 vectors of 2^16 terms, 10.92 / 11.33 / 11.47 / 11.99 ms at 256 of 2^12 and
+// 11.35 / 11.85 / 12.76 / 15.57 ms at 8 of 2^18 (profiles/msm_prepared_batch/).
+static uint32_t msm_parts_batch(size_t k) {
+    static const uint32_t parts = [] {
+        const char* v = getenv("PA_MSM_BATCH_PARTS");
+        const int q = v ? atoi(v) : 1;
+        return (uint32_t)(q < 1 ? 1 : (q > (int)kMsmMaxParts ? (int)kMsmMaxParts : q));
+    }();
+    return parts < k ? parts : (uint32_t)k;
+}
+
 // `n` terms per window; the windows cover 257 bits for the plain entries (a
 // 256-bit FrRepr and the last carry), 130 for the GLV halves (glv; < 2^129).
 // own_basefl: the workspace holds the per-call converted bases.
-static hipError_t msm_plan(MsmPlan& p, int group, size_t n, bool glv = false, bool own_basefl = true) {
-    p.c = glv ? msm_window_bits_glv(n) : msm_window_bits(n);
+// k > 1: a batch of k scalar vectors over the same bases, k W windows.
+static hipError_t msm_plan(MsmPlan& p, int group, size_t n, bool glv = false, bool own_basefl = true, size_t k = 1) {
+    p.c = glv ? (k > 1 ? msm_window_bits_batch(n) : msm_window_bits_glv(n)) : msm_window_bits(n);
     p.W = ((glv ? 130 : 257) + p.c - 1) / p.c;
     p.B = 1u << (p.c - 1);
+    p.k = k;
+    p.fits = k <= 0xffffffffull / p.W && k * p.W <= 0xffffffffull / n && k * p.W <= 0xffffffffull / p.B;
+    if (k > 1 && !p.fits) return hipErrorInvalidValue;
+    p.WT = k * p.W;
     // A/B knob: PA_MSM_SEG; default 8 buckets per segment for G1, 4 for G2 (G2
     // at 2^16 / 2^18: 5.91 / 9.13 ms with 8, 5.73 / 8.90 with 4; G1 at 2^20: 173
     // vs 163 M terms/s; profiles/r04_msm_g2_lazy.txt)
@@ -245,12 +294,12 @@ static hipError_t msm_plan(MsmPlan& p, int group, size_t n, bool glv = false, bo
     }();
     const uint32_t seg = seg_env ? (uint32_t)seg_env : (group == 1 ? 8u : 4u);
     p.L = p.B < seg ? p.B : seg;  // short segments: the running sums are a latency chain per lane
-    p.items = (size_t)p.W * n;
+    p.items = p.WT * n;
     p.passes = (p.c - 1 + 7) / 8;
     p.tpw = (uint32_t)((n + kSortTile - 1) / kSortTile);
     const size_t jw = 8 * (size_t)(group == 1 ? Grp<1>::JW : Grp<2>::JW);
-    const size_t nb = (size_t)p.W * p.B;
-    const size_t nseg = (size_t)p.W * (p.B / p.L);
+    const size_t nb = p.WT * p.B;
+    const size_t nseg = p.WT * (p.B / p.L);
     size_t off = 0;
     p.off_keys_in = off; off = align256(off + 4 * p.items);
     p.off_keys_out = off; off = align256(off + 4 * p.items);
@@ -261,26 +310,47 @@ static hipError_t msm_plan(MsmPlan& p, int group, size_t n, bool glv = false, bo
     p.off_buckets = off; off = align256(off + jw * nb);
     p.off_segs = off; off = align256(off + jw * nseg);
     p.off_tmp = off; off = align256(off + jw * nseg);
-    p.T = msm_chunk(p.items, msm_parts(p.W));
+    p.T = msm_chunk(p.items, k > 1 ? msm_parts_batch(k) : msm_parts(p.W));
     p.off_cont = off; off = align256(off + jw * ((p.items + p.T - 1) / p.T + 1));
     p.off_basefl = off; off = align256(off + (own_basefl ? 4 * (group == 1 ? 28 : 56) * n : 0));
-    p.off_hist = off; off = align256(off + 4 * (size_t)p.W * 256 * p.tpw);
-    p.off_wtot = off; off = align256(off + 4 * (size_t)p.W);
+    p.off_hist = off; off = align256(off + 4 * p.WT * 256 * p.tpw);
+    p.off_wtot = off; off = align256(off + 4 * p.WT);
     p.off_hacc = off; off = align256(off + jw * kMsmMaxParts);
     p.off_long = off; off = align256(off + 4 * (nb + kMsmMaxParts));   // long-bucket lists + counts
+    p.off_wpre = off; off = align256(off + 4 * (p.WT + 1));            // exclusive prefix of wtot
     p.total = off;
     return hipSuccess;
 }
 
-__global__ void __launch_bounds__(256) k_msm_digits(const uint64_t* __restrict__ scalars, size_t n, uint32_t c,
-                                                    uint32_t W, uint32_t B, uint32_t* __restrict__ keys,
-                                                    uint32_t* __restrict__ vals) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint64_t k[4];
+// A scalar row as the digit kernels read it: the canonical words, or with
+// mont the Montgomery form of a value below r taken through into_repr.
+PA_DEV void msm_load_scalar(uint64_t (&k)[4], const uint64_t* __restrict__ row, bool mont) {
 #pragma unroll
-    for (int w = 0; w < 4; w++) k[w] = scalars[4 * i + w];
-    const uint32_t sentinel = W * B;
+    for (int w = 0; w < 4; w++) k[w] = row[w];
+    if (mont) {
+        Fr a, r;
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            a.w[2 * w] = (uint32_t)k[w];
+            a.w[2 * w + 1] = (uint32_t)(k[w] >> 32);
+        }
+        fr_into_repr(r, a);
+#pragma unroll
+        for (int w = 0; w < 4; w++) k[w] = (uint64_t)r.w[2 * w] | ((uint64_t)r.w[2 * w + 1] << 32);
+    }
+}
+
+// `vectors` scalar vectors of n rows end to end; vector j's window w is window
+// j W + w of the pipeline (win0 = j W), over the same n terms.
+__global__ void __launch_bounds__(256) k_msm_digits(const uint64_t* __restrict__ scalars, size_t n, size_t vectors,
+                                                    bool mont, uint32_t c, uint32_t W, uint32_t B, uint32_t sentinel,
+                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * vectors) return;
+    const size_t vec = t / n, i = t - vec * n;
+    const uint32_t win0 = (uint32_t)vec * W;
+    uint64_t k[4];
+    msm_load_scalar(k, scalars + 4 * t, mont);
     const uint32_t mask = (1u << c) - 1;
     uint32_t carry = 0;
     for (uint32_t w = 0; w < W; w++) {
@@ -301,13 +371,13 @@ __global__ void __launch_bounds__(256) k_msm_digits(const uint64_t* __restrict__
             d = (int)raw;
             carry = 0;
         }
-        const size_t at = (size_t)w * n + i;
+        const size_t at = (size_t)(win0 + w) * n + i;
         if (d == 0) {
             keys[at] = sentinel;
             vals[at] = (uint32_t)i;
         } else {
             const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-            keys[at] = w * B + (mag - 1);
+            keys[at] = (win0 + w) * B + (mag - 1);
             vals[at] = (uint32_t)i | (d < 0 ? 0x80000000u : 0u);
         }
     }
@@ -319,15 +389,16 @@ __global__ void __launch_bounds__(256) k_msm_digits(const uint64_t* __restrict__
 // halves are below 2^129 and c W >= 130, so the top window's raw digit is
 // below 2^(c-1): with the carry at most B, never a carry out.
 __global__ void __launch_bounds__(256) k_msm_digits_glv(const uint64_t* __restrict__ scalars, size_t m,
-                                                        uint32_t row_off, uint32_t c, uint32_t W, uint32_t B,
+                                                        size_t vectors, bool mont, uint32_t row_off, uint32_t c,
+                                                        uint32_t W, uint32_t B, uint32_t sentinel,
                                                         uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m * vectors) return;
+    const size_t vec = t / m, i = t - vec * m;
+    const uint32_t win0 = (uint32_t)vec * W;
     uint64_t k[4], half[2][3];
-#pragma unroll
-    for (int w = 0; w < 4; w++) k[w] = scalars[4 * i + w];
+    msm_load_scalar(k, scalars + 4 * t, mont);
     glv_split(k, half[0], half[1]);
-    const uint32_t sentinel = W * B;
     const uint32_t mask = (1u << c) - 1;
     const size_t nt = 2 * m;
 #pragma unroll
@@ -356,13 +427,13 @@ __global__ void __launch_bounds__(256) k_msm_digits_glv(const uint64_t* __restri
                 d = (int)raw;
                 carry = 0;
             }
-            const size_t at = (size_t)w * nt + term;
+            const size_t at = (size_t)(win0 + w) * nt + term;
             if (d == 0) {
                 keys[at] = sentinel;
                 vals[at] = row;
             } else {
                 const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-                keys[at] = w * B + (mag - 1);
+                keys[at] = (win0 + w) * B + (mag - 1);
                 vals[at] = row | (d < 0 ? 0x80000000u : 0u);
             }
         }
@@ -385,16 +456,36 @@ __global__ void __launch_bounds__(256) k_msm_bucket_bounds(const uint32_t* __res
 // items of each window by the 8-bit digit ((key & (B-1)) >> 8k), stably; the
 // first pass reads the window-major digit output (window w at [w*n, w*n + n),
 // zero digits carry key >= sentinel and are skipped), every pass writes the
-// windows compacted (window w at [wbase(w), wbase(w) + wtot[w])).  A window's
+// windows compacted (window w at [wpre[w], wpre[w] + wtot[w])).  A window's
 // source range is cut in tiles of kSortTile items; hist[w][digit][tile] holds
 // the tile's digit counts, and after k_sort_scan the exclusive prefix over
 // (digit, tile) in that order -- where the tile's run of each digit starts.
 
-// window w's first item in the compacted layout
-PA_DEV uint32_t sort_wbase(const uint32_t* __restrict__ wtot, uint32_t w) {
-    uint32_t b = 0;
-    for (uint32_t k = 0; k < w; k++) b += wtot[k];
-    return b;
+// Window w's first item in the compacted layout is wpre[w], the exclusive
+// prefix of wtot (wpre[windows] = every window's items).  A pass moves every
+// nonzero item, so wtot and its prefix are the same after each pass: the
+// prefix is written once, after the first pass's k_sort_scan.  One block.
+__global__ void __launch_bounds__(1024) k_sort_wprefix(const uint32_t* __restrict__ wtot, uint32_t windows,
+                                                       uint32_t* __restrict__ wpre) {
+    __shared__ uint32_t s[2][1024];
+    const uint32_t tid = threadIdx.x, nt = blockDim.x;
+    uint32_t carry = 0;
+    for (uint32_t seg = 0; seg < windows; seg += nt) {
+        const uint32_t idx = seg + tid;
+        const uint32_t v = idx < windows ? wtot[idx] : 0u;
+        s[0][tid] = v;
+        __syncthreads();
+        int cur = 0;
+        for (uint32_t d = 1; d < nt; d <<= 1) {  // inclusive Hillis-Steele scan
+            s[cur ^ 1][tid] = s[cur][tid] + (tid >= d ? s[cur][tid - d] : 0u);
+            cur ^= 1;
+            __syncthreads();
+        }
+        if (idx < windows) wpre[idx] = carry + s[cur][tid] - v;
+        carry += s[cur][nt - 1];
+        __syncthreads();  // s is rewritten by the next segment
+    }
+    if (tid == 0) wpre[windows] = carry;
 }
 
 struct SortPass {
@@ -404,26 +495,27 @@ struct SortPass {
 
 // window w's source range [base, base + count); tile t is its items
 // [t kSortTile, (t + 1) kSortTile) clipped to count
-PA_DEV void sort_window(const SortPass& sp, const uint32_t* __restrict__ wtot, uint32_t w, size_t& base,
-                        uint32_t& count) {
+PA_DEV void sort_window(const SortPass& sp, const uint32_t* __restrict__ wtot, const uint32_t* __restrict__ wpre,
+                        uint32_t w, size_t& base, uint32_t& count) {
     if (sp.first) {
         base = (size_t)w * sp.n;
         count = (uint32_t)sp.n;
     } else {
-        base = sort_wbase(wtot, w);
+        base = wpre[w];
         count = wtot[w];
     }
 }
 
 __global__ void __launch_bounds__(256) k_sort_hist(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ wtot,
-                                                   SortPass sp, uint32_t* __restrict__ hist) {
+                                                   const uint32_t* __restrict__ wpre, SortPass sp,
+                                                   uint32_t* __restrict__ hist) {
     __shared__ uint32_t h[256];
     const uint32_t tid = threadIdx.x, w = blockIdx.x / sp.tpw, t = blockIdx.x % sp.tpw;
     h[tid] = 0;
     __syncthreads();
     size_t base;
     uint32_t count;
-    sort_window(sp, wtot, w, base, count);
+    sort_window(sp, wtot, wpre, w, base, count);
     const uint32_t lo = t * kSortTile;
     uint32_t key[kSortIpt];  // the whole tile's loads in flight at once
 #pragma unroll
@@ -492,7 +584,8 @@ __global__ void __launch_bounds__(1024) k_sort_scan(uint32_t* __restrict__ hist,
 __global__ void __launch_bounds__(256) k_sort_scatter(const uint32_t* __restrict__ keys_in,
                                                       const uint32_t* __restrict__ vals_in,
                                                       const uint32_t* __restrict__ hist,
-                                                      const uint32_t* __restrict__ wtot, SortPass sp,
+                                                      const uint32_t* __restrict__ wtot,
+                                                      const uint32_t* __restrict__ wpre, SortPass sp,
                                                       uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
     __shared__ uint32_t gbase[256], loff[256], wcnt[4][256], scan[2][256];
     __shared__ uint32_t sk[kSortTile], sv[kSortTile];
@@ -501,7 +594,7 @@ __global__ void __launch_bounds__(256) k_sort_scatter(const uint32_t* __restrict
     const uint32_t wave = tid >> 6, lane = tid & 63;
     size_t base;
     uint32_t count;
-    sort_window(sp, wtot, w, base, count);
+    sort_window(sp, wtot, wpre, w, base, count);
     const uint32_t lo = t * kSortTile + wave * (64 * kSortIpt);
     uint32_t keyr[kSortIpt], valr[kSortIpt];  // the wave's loads in flight at once
 #pragma unroll
@@ -514,7 +607,7 @@ __global__ void __launch_bounds__(256) k_sort_scatter(const uint32_t* __restrict
             valr[r] = vals_in[base + k];
         }
     }
-    if (tid == 0) wb_s = sort_wbase(wtot, w);
+    if (tid == 0) wb_s = wpre[w];
     // this tile's digit counts from the prefix: next entry (digit-major) minus this one
     const size_t flat = (size_t)tid * sp.tpw + t, len = (size_t)256 * sp.tpw;
     const uint32_t* hw = hist + (size_t)w * len;
@@ -595,9 +688,9 @@ __global__ void __launch_bounds__(256) k_sort_scatter(const uint32_t* __restrict
 // the part's items [jlo, jhi) of the sorted (window-compacted) array, k0 =
 // floor(jlo / T).  A window's items start with a new bucket, so a chunk
 // straddling two parts is split cleanly (its second piece never writes cont[k]).
-PA_DEV bool chunk_range(size_t i, const uint32_t* __restrict__ wtot, uint32_t w0, uint32_t w1, uint32_t T,
+PA_DEV bool chunk_range(size_t i, const uint32_t* __restrict__ wpre, uint32_t w0, uint32_t w1, uint32_t T,
                         size_t& k, size_t& j0, size_t& j1) {
-    const size_t jlo = sort_wbase(wtot, w0), jhi = sort_wbase(wtot, w1);
+    const size_t jlo = wpre[w0], jhi = wpre[w1];
     k = jlo / T + i;
     j0 = k * T;
     j1 = j0 + T;
@@ -620,12 +713,12 @@ __global__ void __launch_bounds__(64) k_msm_chunk_acc(const uint64_t* __restrict
                                                       const uint32_t* __restrict__ keys,
                                                       const uint32_t* __restrict__ vals,
                                                       const uint32_t* __restrict__ start,
-                                                      const uint32_t* __restrict__ wtot, uint32_t w0, uint32_t w1,
+                                                      const uint32_t* __restrict__ wpre, uint32_t w0, uint32_t w1,
                                                       uint32_t T, uint32_t sentinel, uint64_t* __restrict__ buckets,
                                                       uint64_t* __restrict__ cont) {
     using F = typename Grp<G>::F;
     size_t k, j0, j1;
-    if (!chunk_range((size_t)blockIdx.x * blockDim.x + threadIdx.x, wtot, w0, w1, T, k, j0, j1)) return;
+    if (!chunk_range((size_t)blockIdx.x * blockDim.x + threadIdx.x, wpre, w0, w1, T, k, j0, j1)) return;
     uint32_t cur = keys[j0];
     if (cur >= sentinel) return;  // zero digits sort last
     Jac<F> acc;
@@ -721,11 +814,11 @@ PA_DEV void msm_flush_fl(uint32_t key, const FlJac& acc, bool untouched, size_t 
 template <bool PREFETCH>
 PA_DEV void chunk_acc_fl_body(const uint32_t* __restrict__ basefl, const uint32_t* __restrict__ keys,
                                               const uint32_t* __restrict__ vals, const uint32_t* __restrict__ start,
-                                              const uint32_t* __restrict__ wtot, uint32_t w0, uint32_t w1,
+                                              const uint32_t* __restrict__ wpre, uint32_t w0, uint32_t w1,
                                               uint32_t T, uint32_t sentinel, uint64_t* __restrict__ buckets,
                                               uint64_t* __restrict__ cont) {
     size_t k, j0, j1;
-    if (!chunk_range((size_t)blockIdx.x * blockDim.x + threadIdx.x, wtot, w0, w1, T, k, j0, j1)) return;
+    if (!chunk_range((size_t)blockIdx.x * blockDim.x + threadIdx.x, wpre, w0, w1, T, k, j0, j1)) return;
     uint32_t cur = keys[j0];
     if (cur >= sentinel) return;
     FlJac acc;
@@ -799,20 +892,20 @@ PA_DEV void chunk_acc_fl_body(const uint32_t* __restrict__ basefl, const uint32_
 }
 #define PA_CHUNK_ACC_FL_ARGS                                                                                   \
     const uint32_t *__restrict__ basefl, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals, \
-        const uint32_t *__restrict__ start, const uint32_t *__restrict__ wtot, uint32_t w0, uint32_t w1,      \
+        const uint32_t *__restrict__ start, const uint32_t *__restrict__ wpre, uint32_t w0, uint32_t w1,      \
         uint32_t T, uint32_t sentinel, uint64_t *__restrict__ buckets, uint64_t *__restrict__ cont
 // one wave per SIMD (256 VGPRs + 75 AGPRs), the base prefetched
 __global__ void __launch_bounds__(64) PA_MSM_ACC_ATTR k_msm_chunk_acc_fl(PA_CHUNK_ACC_FL_ARGS) {
-    chunk_acc_fl_body<true>(basefl, keys, vals, start, wtot, w0, w1, T, sentinel, buckets, cont);
+    chunk_acc_fl_body<true>(basefl, keys, vals, start, wpre, w0, w1, T, sentinel, buckets, cont);
 }
 // two waves per SIMD (256 registers), the gathers hidden by the other wave
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_msm_chunk_acc_fl_2w(PA_CHUNK_ACC_FL_ARGS) {
-    chunk_acc_fl_body<false>(basefl, keys, vals, start, wtot, w0, w1, T, sentinel, buckets, cont);
+    chunk_acc_fl_body<false>(basefl, keys, vals, start, wpre, w0, w1, T, sentinel, buckets, cont);
 }
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_msm_chunk_acc_fl_2wp(PA_CHUNK_ACC_FL_ARGS) {
-    chunk_acc_fl_body<true>(basefl, keys, vals, start, wtot, w0, w1, T, sentinel, buckets, cont);
+    chunk_acc_fl_body<true>(basefl, keys, vals, start, wpre, w0, w1, T, sentinel, buckets, cont);
 }
 
 
@@ -1060,6 +1153,36 @@ __global__ void __launch_bounds__(64) k_msm_horner_q(const uint64_t* __restrict_
     store_jac_q(out, acc, lane == 0);
 }
 
+// The batch's Horner (G1): vector j of [j0, j1) on its own group of 4 quads,
+// four groups per wave, over its windows j W + w from the top down as
+// k_msm_horner_q does; the point goes to out + JW j.  A vector whose window
+// sums are all zero keeps the zero point it loaded.
+constexpr unsigned kHornerPerWave = 4;
+__global__ void __launch_bounds__(64) k_msm_horner_batch_q(const uint64_t* __restrict__ wsum, uint32_t stride,
+                                                           uint32_t W, uint32_t c, size_t j0, size_t j1,
+                                                           uint64_t* __restrict__ out) {
+    constexpr int NQ = 4, L = 4 * NQ, JW = Grp<1>::JW;
+    static_assert(64 / L == kHornerPerWave, "groups per wave");
+    const int lane = threadIdx.x;
+    const size_t j = j0 + (size_t)blockIdx.x * kHornerPerWave + lane / L;
+    if (j >= j1) return;   // whole groups leave together
+    const dq::Lc l = dq::lctx(lane, NQ);
+    const uint64_t* ws = wsum + (size_t)JW * stride * (j * W);
+    dq::Jq<dq::Q> acc;
+    load_jac_q(acc, ws + (size_t)JW * stride * (W - 1), l);
+#pragma unroll 1
+    for (int w = (int)W - 2; w >= 0; w--) {
+        if (!dq::is_zero(acc.z)) {
+#pragma unroll 1
+            for (uint32_t k = 0; k < c; k++) dq::jdbl<NQ>(acc, l);
+        }
+        dq::Jq<dq::Q> x;
+        load_jac_q(x, ws + (size_t)JW * stride * w, l);
+        if (!dq::is_zero(x.z)) dq::jadd<NQ>(acc, dq::make_fixed<NQ>(x, l), l);
+    }
+    store_jac_q(out + (size_t)JW * j, acc, lane % L == 0);
+}
+
 // k_msm_segments<1> on the lazy core (same sums, same formulas)
 __global__ void __launch_bounds__(64) k_msm_segments_fl(const uint64_t* __restrict__ buckets, uint32_t B, uint32_t L,
                                                         size_t t0, size_t t1, uint64_t* __restrict__ segs) {
@@ -1135,11 +1258,11 @@ __global__ void __launch_bounds__(64) k_msm_chunk_acc_fl2(const uint32_t* __rest
                                                           const uint32_t* __restrict__ keys,
                                                           const uint32_t* __restrict__ vals,
                                                           const uint32_t* __restrict__ start,
-                                                          const uint32_t* __restrict__ wtot, uint32_t w0, uint32_t w1,
+                                                          const uint32_t* __restrict__ wpre, uint32_t w0, uint32_t w1,
                                                           uint32_t T, uint32_t sentinel,
                                                           uint64_t* __restrict__ buckets, uint64_t* __restrict__ cont) {
     size_t k, j0, j1;
-    if (!chunk_range((size_t)blockIdx.x * blockDim.x + threadIdx.x, wtot, w0, w1, T, k, j0, j1)) return;
+    if (!chunk_range((size_t)blockIdx.x * blockDim.x + threadIdx.x, wpre, w0, w1, T, k, j0, j1)) return;
     uint32_t cur = keys[j0];
     if (cur >= sentinel) return;
     FlJac2 acc = fl2_jac_zero();
@@ -1297,12 +1420,13 @@ __global__ void __launch_bounds__(LazyJac<G>::NT) k_msm_long_fix(const uint32_t*
 }
 
 template <int G>
-__global__ void __launch_bounds__(64) k_jac_zero_out(uint64_t* __restrict__ out) {
+__global__ void __launch_bounds__(64) k_jac_zero_out(uint64_t* __restrict__ out, size_t count) {
     using F = typename Grp<G>::F;
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
     Jac<F> z;
     jac_zero(z);
-    store_jac(out, z);
+    store_jac(out + (size_t)Grp<G>::JW * i, z);
 }
 
 static inline unsigned msm_blocks(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
@@ -1318,6 +1442,17 @@ size_t msm_prepared_workspace_bytes(size_t m, bool glv) {
     if (m == 0) return 0;
     MsmPlan p;
     if (msm_plan(p, 1, glv ? 2 * m : m, glv, false) != hipSuccess) return 0;
+    return p.total;
+}
+bool msm_prepared_batch_fits(size_t m, size_t k, bool glv) {
+    if (m == 0 || k == 0) return true;
+    MsmPlan p;
+    return msm_plan(p, 1, glv ? 2 * m : m, glv, false, k) == hipSuccess && p.fits;
+}
+size_t msm_prepared_batch_workspace_bytes(size_t m, size_t k, bool glv) {
+    if (m == 0 || k == 0) return 0;
+    MsmPlan p;
+    if (msm_plan(p, 1, glv ? 2 * m : m, glv, false, k) != hipSuccess || !p.fits) return 0;
     return p.total;
 }
 
@@ -1365,22 +1500,26 @@ struct MsmJob {
     size_t terms;
     size_t row_off;
     bool glv;
+    size_t vectors = 1;   // scalar vectors of `terms` rows end to end, one output each
+    bool mont = false;    // the scalar rows are Montgomery Fr (< r), not FrRepr
 };
 
 template <int G>
 static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_bytes, hipStream_t s) {
     constexpr int JW = Grp<G>::JW;
+    if (job.vectors == 0) return hipSuccess;
     if (job.terms == 0) {
-        hipLaunchKernelGGL(k_jac_zero_out<G>, dim3(1), dim3(64), 0, s, out);
+        hipLaunchKernelGGL(k_jac_zero_out<G>, dim3(msm_blocks(job.vectors, 64)), dim3(64), 0, s, out, job.vectors);
         return hipGetLastError();
     }
     const uint64_t* bases = job.bases;
     const size_t n = job.glv ? 2 * job.terms : job.terms;   // items per window
     MsmPlan p;
-    hipError_t e = msm_plan(p, G, n, job.glv, job.rows == nullptr);
+    hipError_t e = msm_plan(p, G, n, job.glv, job.rows == nullptr, job.vectors);
     if (e != hipSuccess) return e;
     if (ws_bytes < p.total || !ws) return hipErrorInvalidValue;
-    if (p.items > 0xffffffffull) return hipErrorInvalidValue;  // 32-bit item positions
+    if (!p.fits || p.items > 0xffffffffull) return hipErrorInvalidValue;  // 32-bit item positions and keys
+    const uint32_t WT = (uint32_t)p.WT, sentinel = WT * p.B;
     char* base = static_cast<char*>(ws);
     uint32_t* keys_in = reinterpret_cast<uint32_t*>(base + p.off_keys_in);
     uint32_t* keys_out = reinterpret_cast<uint32_t*>(base + p.off_keys_out);
@@ -1391,27 +1530,32 @@ static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_
     uint64_t* buckets = reinterpret_cast<uint64_t*>(base + p.off_buckets);
     uint64_t* segs = reinterpret_cast<uint64_t*>(base + p.off_segs);
     uint64_t* tmp = reinterpret_cast<uint64_t*>(base + p.off_tmp);
-    const size_t nb = (size_t)p.W * p.B;
+    const size_t nb = p.WT * p.B;
 
     if (job.glv)
-        hipLaunchKernelGGL(k_msm_digits_glv, dim3(msm_blocks(job.terms, 256)), dim3(256), 0, s, job.scalars, job.terms,
-                           (uint32_t)job.row_off, p.c, p.W, p.B, keys_in, vals_in);
+        hipLaunchKernelGGL(k_msm_digits_glv, dim3(msm_blocks(job.terms * job.vectors, 256)), dim3(256), 0, s,
+                           job.scalars, job.terms, job.vectors, job.mont, (uint32_t)job.row_off, p.c, p.W, p.B,
+                           sentinel, keys_in, vals_in);
     else
-        hipLaunchKernelGGL(k_msm_digits, dim3(msm_blocks(n, 256)), dim3(256), 0, s, job.scalars, n, p.c, p.W, p.B,
-                           keys_in, vals_in);
+        hipLaunchKernelGGL(k_msm_digits, dim3(msm_blocks(n * job.vectors, 256)), dim3(256), 0, s, job.scalars, n,
+                           job.vectors, job.mont, p.c, p.W, p.B, sentinel, keys_in, vals_in);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // the bucketing sort: ping-pong between the _in and _out arrays; the last
     // destination's tail past the nonzero items is set to sentinel keys first
     uint32_t* hist = reinterpret_cast<uint32_t*>(base + p.off_hist);
     uint32_t* wtot = reinterpret_cast<uint32_t*>(base + p.off_wtot);
+    uint32_t* wpre = reinterpret_cast<uint32_t*>(base + p.off_wpre);
     uint32_t *ksrc = keys_in, *vsrc = vals_in, *kdst = keys_out, *vdst = vals_out;
-    const unsigned tiles = p.W * p.tpw;
+    if ((size_t)WT * p.tpw > 0x7fffffffull) return hipErrorInvalidValue;   // the sort's grid
+    const unsigned tiles = WT * p.tpw;
     for (uint32_t pass = 0; pass < p.passes; pass++) {
-        const SortPass sp{8 * pass, p.B - 1, p.W * p.B, p.tpw, pass == 0 ? 1u : 0u, n};
-        hipLaunchKernelGGL(k_sort_hist, dim3(tiles), dim3(256), 0, s, ksrc, wtot, sp, hist);
-        hipLaunchKernelGGL(k_sort_scan, dim3(p.W), dim3(1024), 0, s, hist, p.tpw, wtot);
+        const SortPass sp{8 * pass, p.B - 1, sentinel, p.tpw, pass == 0 ? 1u : 0u, n};
+        hipLaunchKernelGGL(k_sort_hist, dim3(tiles), dim3(256), 0, s, ksrc, wtot, wpre, sp, hist);
+        hipLaunchKernelGGL(k_sort_scan, dim3(WT), dim3(1024), 0, s, hist, p.tpw, wtot);
+        if (pass == 0)   // the same totals after every pass
+            hipLaunchKernelGGL(k_sort_wprefix, dim3(1), dim3(WT <= 64 ? 64 : 1024), 0, s, wtot, WT, wpre);
         if (pass + 1 == p.passes && (e = hipMemsetAsync(kdst, 0xff, 4 * p.items, s)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_sort_scatter, dim3(tiles), dim3(256), 0, s, ksrc, vsrc, hist, wtot, sp, kdst, vdst);
+        hipLaunchKernelGGL(k_sort_scatter, dim3(tiles), dim3(256), 0, s, ksrc, vsrc, hist, wtot, wpre, sp, kdst, vdst);
         std::swap(ksrc, kdst);
         std::swap(vsrc, vdst);
     }
@@ -1420,7 +1564,7 @@ static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_
     if ((e = hipMemsetAsync(start, 0, 4 * nb, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(end, 0, 4 * nb, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_msm_bucket_bounds, dim3(msm_blocks(p.items, 256)), dim3(256), 0, s, keys_out, p.items,
-                       p.W * p.B, start, end);
+                       sentinel, start, end);
     uint64_t* cont = reinterpret_cast<uint64_t*>(base + p.off_cont);
     uint64_t* hacc = reinterpret_cast<uint64_t*>(base + p.off_hacc);
     const uint32_t* basefl = job.rows ? job.rows : reinterpret_cast<const uint32_t*>(base + p.off_basefl);
@@ -1451,7 +1595,7 @@ static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_
     for (uint32_t count = spw; count > 1; count = (count + group - 1) / group) wsum = wsum == segs ? tmp : segs;
 
     // the windows' throughput kernels of one part (windows [w0, w1))
-    // (the part's item range is on the device, wtot: lanes for the most it can hold)
+    // (the part's item range is on the device, wpre: lanes for the most it can hold)
     // the G1 bucket accumulation's kernel: PA_MSM_ACC=0 one wave per SIMD with
     // the base prefetch, 1 two waves without it, 2 two waves with it (A/B)
     static const int acc_kind = [] {
@@ -1463,14 +1607,14 @@ static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_
         if constexpr (G == 1)
             hipLaunchKernelGGL(acc_kind == 1 ? k_msm_chunk_acc_fl_2w
                                              : (acc_kind == 2 ? k_msm_chunk_acc_fl_2wp : k_msm_chunk_acc_fl),
-                               dim3(msm_blocks(chunks, 64)), dim3(64), 0, st, basefl, keys_out, vals_out, start, wtot,
-                               w0, w1, p.T, p.W * p.B, buckets, cont);
+                               dim3(msm_blocks(chunks, 64)), dim3(64), 0, st, basefl, keys_out, vals_out, start, wpre,
+                               w0, w1, p.T, sentinel, buckets, cont);
         else if (g2_lazy)
             hipLaunchKernelGGL(k_msm_chunk_acc_fl2, dim3(msm_blocks(chunks, 64)), dim3(64), 0, st, basefl, keys_out,
-                               vals_out, start, wtot, w0, w1, p.T, p.W * p.B, buckets, cont);
+                               vals_out, start, wpre, w0, w1, p.T, sentinel, buckets, cont);
         else
             hipLaunchKernelGGL(k_msm_chunk_acc<G>, dim3(msm_blocks(chunks, 64)), dim3(64), 0, st, bases, keys_out,
-                               vals_out, start, wtot, w0, w1, p.T, p.W * p.B, buckets, cont);
+                               vals_out, start, wpre, w0, w1, p.T, sentinel, buckets, cont);
         return hipGetLastError();
     };
     // ... and its bucket -> window-sum reduction
@@ -1528,6 +1672,57 @@ static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_
                                t0, t1, segs);
         return group_levels(w0, w1, st);
     };
+
+    // A batch: parts are ranges of vectors, [v0, v1) = windows [v0 W, v1 W), so
+    // every vector's Horner chain completes inside its part (k_msm_horner_batch_q
+    // writes out + JW j) and nothing is carried between parts.  One part by
+    // default (msm_parts_batch).  With more, the caller's stream accumulates part
+    // after part; the reduction and Horner grid of every part but the last run
+    // behind it on the side streams, in turn.
+    if (job.vectors > 1) {
+        if constexpr (G != 1) return hipErrorInvalidValue;   // prepared G1 rows only
+        const size_t k = job.vectors;
+        const uint32_t parts = msm_parts_batch(k);
+        auto horner = [&](size_t v0, size_t v1, hipStream_t st) {
+            hipLaunchKernelGGL(k_msm_horner_batch_q, dim3(msm_blocks(v1 - v0, kHornerPerWave)), dim3(64), 0, st, wsum,
+                               spw, p.W, p.c, v0, v1, out);
+            return hipGetLastError();
+        };
+        if (parts == 1) {
+            if ((e = accumulate(0, WT, s)) != hipSuccess || (e = reduce(0, WT, 0, s)) != hipSuccess) return e;
+            return horner(0, k, s);
+        }
+        hipStream_t side[2];
+        if ((e = msm_side_streams(s, side)) != hipSuccess) return e;
+        hipEvent_t ev[2 * kMsmMaxParts] = {};   // ev[2q]: part q accumulated; ev[2q + 1]: its outputs written
+        int made = 0;
+        hipError_t err = hipSuccess;
+        auto ck = [&](hipError_t x) {
+            if (err == hipSuccess) err = x;
+            return err == hipSuccess;
+        };
+        for (; made < 2 * (int)(parts - 1); made++)
+            if (!ck(hipEventCreateWithFlags(&ev[made], hipEventDisableTiming))) break;
+        for (uint32_t q = 0; q < parts && err == hipSuccess; q++) {
+            const size_t v0 = k * q / parts, v1 = k * (q + 1) / parts;
+            const uint32_t w0 = (uint32_t)v0 * p.W, w1 = (uint32_t)v1 * p.W;
+            if (!ck(accumulate(w0, w1, s))) break;
+            if (q + 1 == parts) {
+                if (ck(reduce(w0, w1, q, s))) ck(horner(v0, v1, s));
+                break;
+            }
+            hipStream_t st = side[q & 1];
+            if (!ck(hipEventRecord(ev[2 * q], s)) || !ck(hipStreamWaitEvent(st, ev[2 * q], 0)) ||
+                !ck(reduce(w0, w1, q, st)) || !ck(horner(v0, v1, st)))
+                break;
+            ck(hipEventRecord(ev[2 * q + 1], st));
+        }
+        for (uint32_t q = 0; q + 1 < parts && err == hipSuccess; q++) ck(hipStreamWaitEvent(s, ev[2 * q + 1], 0));
+        if (err != hipSuccess)   // let what this call queued on the side streams drain (see below)
+            for (hipStream_t x : side) (void)hipStreamSynchronize(x);
+        for (int i = 0; i < made; i++) (void)hipEventDestroy(ev[i]);
+        return err;
+    }
 
     // the round-3 one-wave Horner kernels (PA_MSM_HORNER=1: three-lane
     // doublings, G1 on the lazy core) run the whole MSM as one part
@@ -1648,6 +1843,16 @@ hipError_t launch_msm_prepared_g1(const uint32_t* rows, size_t len, bool glv, co
                                   uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream) {
     if (len >= kMsmPreparedMax || m > len) return hipErrorInvalidValue;
     const MsmJob job{nullptr, rows, scalars, m, len, glv};
+    return msm_run<1>(job, out, ws, ws_bytes, stream);
+}
+
+hipError_t launch_msm_prepared_g1_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
+                                        size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
+                                        hipStream_t stream) {
+    if (len >= kMsmPreparedMax || m > len) return hipErrorInvalidValue;
+    MsmJob job{nullptr, rows, scalars, m, len, glv};
+    job.vectors = k;
+    job.mont = mont;
     return msm_run<1>(job, out, ws, ws_bytes, stream);
 }
 

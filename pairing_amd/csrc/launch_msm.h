@@ -37,4 +37,16 @@ size_t msm_prepared_workspace_bytes(size_t m, bool glv);
 hipError_t launch_msm_prepared_g1(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
                                   uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream);
 
+// out[j] = sum_{i < m} scalars[j m + i] * P_i for j < k: k vectors end to end
+// through one pipeline of k W windows.  mont: the rows are Montgomery Fr below
+// r (what the NTT writes) and pass through into_repr first.  Item positions
+// and keys are 32-bit: msm_prepared_batch_fits says whether k W nt <= 2^32 - 1
+// and k W B < 2^32 hold for the plan of (m, k); a batch that does not fit has
+// workspace size 0 and is refused.
+bool msm_prepared_batch_fits(size_t m, size_t k, bool glv);
+size_t msm_prepared_batch_workspace_bytes(size_t m, size_t k, bool glv);
+hipError_t launch_msm_prepared_g1_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
+                                        size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
+                                        hipStream_t stream);
+
 }  // namespace pa

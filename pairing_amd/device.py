@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, FrNttDomain, G1MsmBases, _lib, call, csr_offsets, ntt_mode
+from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, FrNttDomain, G1MsmBases, _lib, call, csr_offsets, msm_scalars, ntt_mode
 
 
 def _stream_ptr(stream):
@@ -374,6 +374,37 @@ def multiexp_prepared(prepared, scalars, out, workspace, stream=None):
     _rows(out, 1, "out")
     call("pa_g1_multiexp_prepared_device", h, _dptr(scalars, 4, "scalars"), m, _dptr(out, W_G1, "out"),
          ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
+
+
+def multiexp_prepared_batch_workspace(prepared, m, k, device):
+    """A device workspace sized for multiexp_prepared_batch: k vectors over the first m
+    prepared bases.  A batch over the 32-bit item limit (include/pairing_amd.h) is a
+    ValueError: split it."""
+    m, k = int(m), int(k)
+    if k < 0:
+        raise ValueError("k must not be negative, got %d" % k)
+    nbytes = int(_lib.pa_g1_multiexp_prepared_batch_workspace_bytes(prepared.check_terms(m), m, k))
+    if nbytes == 0 and m and k:
+        raise ValueError("a batch of %d vectors of %d terms is over the 32-bit item limit: split it" % (k, m))
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
+def multiexp_prepared_batch(prepared, scalars, m, k, out, workspace, montgomery=False, stream=None):
+    """out[j] (k, 18) = sum_i scalars[j * m + i] * P_i over the first m prepared bases:
+    k vectors end to end in `scalars` ((k * m, 4); FrRepr rows, or with montgomery=True
+    the Montgomery Fr rows fr_ntt writes), each equal as a point to multiexp_prepared
+    over that vector.  Nothing is allocated or read back."""
+    if not isinstance(prepared, G1MsmBases):
+        raise ValueError("prepared must come from msm_prepare")
+    m, k = int(m), int(k)
+    flags = msm_scalars(montgomery)
+    h = prepared.check_terms(m)
+    if k < 0:
+        raise ValueError("k must not be negative, got %d" % k)
+    _rows(scalars, k * m, "scalars")
+    _rows(out, k, "out")
+    call("pa_g1_multiexp_prepared_batch_device", h, _dptr(scalars, 4, "scalars"), m, k, flags,
+         _dptr(out, W_G1, "out"), ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
 
 
 def wnaf_exact_workspace(group, n, window, fixed_scalar, device):
