@@ -4,7 +4,15 @@
 // (fq.rs:22-30, 6 x u64).  Inside the pairing kernels a value is
 // sum w[i] 2^(28 i) with a compile-time bound U:
 //
-//     every limb <= U (2^28 - 1)   and   value < U * 2q          (U <= 16)
+//     every limb <= U (2^28 - 1)   and   value <= U * 2q         (U <= 16)
+//
+// The value bound is strict (value < U * 2q) for everything but one producer:
+// neg of a zero returns the constant C_B itself, and for B = 3, 4, 7, 8, 11,
+// 12, 13 that constant is exactly FL_SUB_CU[B-1] * 2q.  Every consumer holds
+// at equality: red still lands in [0, 2q) (its quotient estimate is good for
+// any V < 2^388 with limbs < 2^32), the leaves have 2^4 of headroom in the
+// value, and the subtraction constants cover the top limb of B * 2q itself
+// (tests/test_fl_model.py, tests/test_fl_unit.py).
 //
 //   * products (leaf subroutines of fl_gen.h) return F<1>; they require
 //     sum(U_x * U_y) <= 17 over their terms (one 64-bit column accumulator)
@@ -13,7 +21,8 @@
 //   * add: limb-wise, no carries, F<A+B>;
 //   * sub: a + C_B - b where C_B = k q has limbs >= any limb of a value of
 //     bound B (FL_SUB_C), F<A + FL_SUB_CU[B-1]>;
-//   * red: one pass that subtracts floor(V/q) (or one less) times q, F<1>.
+//   * red: one pass that subtracts floor(V/q) (or one less) times q, F<1>
+//     with value < 2q, strictly.
 // fl_from_abi / fl_to_abi convert at the kernel boundary (one product each);
 // stores are canonical, so outputs stay bit-identical to the reference's Fq.
 #pragma once

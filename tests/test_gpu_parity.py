@@ -107,6 +107,105 @@ def test_cyclotomic_square_equals_square_in_subgroup(gpu, oracle):
     np.testing.assert_array_equal(gpu.fq12_cyclotomic_square(f), oracle.fq12_square(f))
 
 
+# ---- edge values through the canonical tower ABI (pa_fq2_* / pa_fq6_* / pa_fq12_*) ----
+def _edge_tower(ncoef, seed, n=200):
+    """at most 256 records of ncoef canonical Fq words each: coefficients drawn from
+    _edge_fq(), and the structured patterns -- all coefficients equal, c0 = c1 and
+    c0 = -c1 in every Fq2, all q - 1, sparse -- next to random ones"""
+    import random
+    g = random.Random(seed)
+    edge = [sum(int(w) << (64 * i) for i, w in enumerate(r)) for r in _edge_fq()]
+    pick = lambda: g.choice(edge) if g.randrange(2) else g.randrange(Q)  # noqa: E731
+    recs = [[v] * ncoef for v in edge]
+    x = g.randrange(Q)
+    recs.append([x] * ncoef)
+    for _ in range(6):
+        xs = [pick() for _ in range(ncoef // 2)]
+        recs.append([xs[i // 2] for i in range(ncoef)])
+        recs.append([xs[i // 2] if i % 2 == 0 else (Q - xs[i // 2]) % Q for i in range(ncoef)])
+    for pos in range(ncoef):
+        recs.append([pick() or 1 if i == pos else 0 for i in range(ncoef)])
+    while len(recs) < n:
+        recs.append([g.choice(edge) for _ in range(ncoef)] if len(recs) % 2 else [pick() for _ in range(ncoef)])
+    assert len(recs) <= 256
+    return np.array([sum((limbs(v) for v in r), []) for r in recs], np.uint64)
+
+
+def _plain(rows, ncoef):
+    """rows of canonical Montgomery words -> pymodel elements"""
+    from helpers import unmont
+    out = []
+    for r in rows:
+        c = [unmont(r[6 * k:6 * k + 6]) for k in range(ncoef)]
+        f2 = [(c[2 * k], c[2 * k + 1]) for k in range(ncoef // 2)]
+        out.append(f2[0] if ncoef == 2 else tuple(f2) if ncoef == 6 else (tuple(f2[:3]), tuple(f2[3:])))
+    return out
+
+
+def _embed12(a):
+    e = np.zeros((a.shape[0], 72), np.uint64)
+    e[:, :a.shape[1]] = a
+    return e
+
+
+_TOWER_ENTRIES = ["fq2_mul", "fq2_square", "fq2_inverse", "fq2_frobenius", "fq6_mul", "fq6_square", "fq6_inverse",
+                  "fq6_frobenius", "fq12_mul", "fq12_square", "fq12_inverse", "fq12_frobenius", "fq12_mul_by_014",
+                  "fq12_cyclotomic_square"]
+
+
+@pytest.mark.parametrize("entry", _TOWER_ENTRIES)
+def test_tower_abi_edge_values(gpu, oracle, entry):
+    """the Fq2 / Fq6 / Fq12 entries of the C ABI on edge coefficients (0, 1, 2, q - 1,
+    q - 2, (q - 1) / 2, R, 2^380 - 1) and structured elements, bit-exact against the
+    oracle (subfield entries through the embedding in Fq12) and, independently,
+    against the pure-Python tower model.  The ABI takes canonical words only, so
+    the x + q forms of tests/test_fl_unit.py have no counterpart here."""
+    import fl_ref
+    import pymodel as pm
+    field, op = entry.split("_", 1)
+    ncoef = {"fq2": 2, "fq6": 6, "fq12": 12}[field]
+    w = 6 * ncoef
+    a = _edge_tower(ncoef, 70 + len(entry))
+    b = _edge_tower(ncoef, 71 + len(entry))[::-1].copy()
+    A, B = _plain(a, ncoef), _plain(b, ncoef)
+    mul = {2: pm.f2mul, 6: pm.f6mul, 12: pm.f12mul}[ncoef]
+    inv = {2: pm.f2inv, 6: pm.f6inv, 12: pm.f12inv}[ncoef]
+    frob = {2: fl_ref.f2frob, 6: fl_ref.f6frob, 12: fl_ref.f12frob}[ncoef]
+
+    def same(got, exp_oracle, exp_model, rows=slice(None)):
+        np.testing.assert_array_equal(got[rows], exp_oracle[rows][:, :w])
+        assert _plain(got[rows], ncoef) == exp_model
+
+    if op == "mul":
+        same(getattr(gpu, entry)(a, b), oracle.fq12_mul(_embed12(a), _embed12(b)), [mul(x, y) for x, y in zip(A, B)])
+        same(getattr(gpu, entry)(a, a), oracle.fq12_mul(_embed12(a), _embed12(a)), [mul(x, x) for x in A])
+    elif op == "square":
+        same(getattr(gpu, entry)(a), oracle.fq12_square(_embed12(a)), [mul(x, x) for x in A])
+    elif op == "inverse":
+        got, ok = getattr(gpu, entry)(a)
+        exp, eok = oracle.fq12_inverse(_embed12(a))
+        nz = np.array([any(fl_ref.flat(x)) for x in A])
+        np.testing.assert_array_equal(ok, eok.astype(bool))
+        np.testing.assert_array_equal(ok, nz)
+        assert not ok.all() and ok.any()
+        same(got, exp, [inv(x) for x, k in zip(A, nz) if k], rows=nz)
+    elif op == "frobenius":
+        for power in range({2: 4, 6: 7, 12: 12}[ncoef]):
+            got = getattr(gpu, entry + "_map")(a, power)
+            same(got, oracle.fq12_frobenius(_embed12(a), power), [frob(x, power) for x in A])
+    elif op == "mul_by_014":
+        c0, c1, c4 = (_edge_tower(2, 72 + k, n=a.shape[0])[:a.shape[0]] for k in range(3))
+        C = [_plain(c, 2) for c in (c0, c1, c4)]
+        got = gpu.fq12_mul_by_014(a, c0, c1, c4)
+        same(got, oracle.fq12_mul_by_014(a, c0, c1, c4),
+             [fl_ref.mul_by_014(x, C[0][i], C[1][i], C[2][i]) for i, x in enumerate(A)])
+    else:
+        assert op == "cyclotomic_square"
+        nz = np.array([any(fl_ref.flat(x)) for x in A])
+        f = np.concatenate([_cyclotomic(oracle, np.ascontiguousarray(a[nz])), fq12_one()])
+        same(gpu.fq12_cyclotomic_square(f), oracle.fq12_square(f), [pm.f12sqr(x) for x in _plain(f, 12)])
+
+
 def _points(seed, n, inf_every=0):
     g = rng(seed)
     s1 = random_scalars(g, n)

@@ -5,7 +5,10 @@ Representation "Fl" (lazy Fq): 14 limbs of nominally 28 bits in 32-bit
 registers, value = sum w[i] 2^(28 i), Montgomery radix R = 2^392.  A value
 carries a bound u (tracked by the code that uses it):
 
-    every limb <= u (2^28 - 1)    and    value < u * 2q.
+    every limb <= u (2^28 - 1)    and    value <= u * 2q
+
+(strictly below except for the negation of a zero, which is the constant SUB_C
+itself: for some u that constant is exactly its own bound times 2q -- fl.h).
 
 A Montgomery product returns u = 1 (limbs < 2^28, value < 2q).  Additions are
 limb-wise with no carries (u adds up); a subtraction adds a multiple of q
@@ -47,7 +50,9 @@ U_MAX_SUB = 14  # SUB_C tables for subtrahend bounds 1..U_MAX_SUB
 
 # floor(2^400 / q): with T = x13 2^28 + x12 (< 2^50), k = (T KQ) >> 64 is
 # floor(V / q) or one less for any V < 2^388 with limbs < 2^32 (checked in
-# tests/test_fl_model.py), so V - k q lies in [0, 2q).
+# tests/test_fl_model.py: an exact integer model of fl.h's red at every
+# multiple of q below 2^388, +-1, with normalized and with raised limbs), so
+# V - k q lies in [0, 2q).
 KQ = (1 << 400) // Q
 assert KQ < (1 << 32)
 
