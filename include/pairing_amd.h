@@ -179,7 +179,19 @@ int pa_miller_loop_shared_prepared(const pa_g1_affine *p, size_t n, const pa_g2_
 int pa_multi_miller_loop(const pa_g1_affine *p, const pa_g2_prepared *q, size_t n, pa_fq12 *out);
 /* Engine::final_exponentiation, mod.rs:104-160; ok[i] = 0 iff in[i] == 0 */
 int pa_final_exponentiation_batch(const pa_fq12 *in, pa_fq12 *out, uint8_t *ok, size_t n);
-/* Engine::pairing, lib.rs:101-109: out[i] = e(p[i], q[i]) (prepare fused on device) */
+/* Engine::pairing, lib.rs:101-109: out[i] = e(p[i], q[i]) (prepare fused on device).
+ * Like the reference, no precondition on the points: p[i] and q[i] may be any
+ * field elements (outside the subgroups, of small order, or no curve point at
+ * all, as the unchecked decoders hand them on), and out[i] is the reference's
+ * value for them at every batch size -- a zero record where it is None (Miller
+ * value 0).  Cost of a Q off E': the batches the pairing-only Miller loops
+ * serve (above PA_PQ_MAX pairs) test every Q against the curve in one more
+ * launch (k_pairing_ml_fixup: within run-to-run noise at 2^16 pairs, 15.3 ms)
+ * and recompute an off-curve pair in reference form on one lane -- one serial
+ * Miller loop for the call, 8 to 12 ms whether it holds one such pair or 64
+ * (profiles/pairing_domain/).  The same
+ * holds for pa_multi_pairing*, pa_pairing_batch_device and
+ * pa_pairing_miller_loop_batch_device. */
 int pa_pairing_batch(const pa_g1_affine *p, const pa_g2_affine *q, pa_fq12 *out, size_t n);
 
 /* ---- G1 (config 3: parameter generation) ---- */
@@ -325,7 +337,8 @@ int pa_fq2_sqrt_batch(const pa_fq2 *a, pa_fq2 *out, uint8_t *ok, size_t n);
  * device -- = the product of the per-pair loops (mod.rs:40-102); then, for
  * pa_multi_pairing, Engine::final_exponentiation (mod.rs:104-160): the
  * batch-verification shape e(P_1,Q_1)...e(P_n,Q_n).  ok = 0 iff the product
- * Miller value is zero (None). */
+ * Miller value is zero (None).  The points may be any field elements, as for
+ * pa_pairing_batch (a Q off E' costs what it costs there). */
 int pa_multi_miller_loop_affine(const pa_g1_affine *p, const pa_g2_affine *q, size_t n, pa_fq12 *out);
 int pa_multi_pairing(const pa_g1_affine *p, const pa_g2_affine *q, size_t n, pa_fq12 *out, uint8_t *ok);
 /* m independent pa_multi_pairing products in one call -- a batch of signature
@@ -568,7 +581,11 @@ int pa_miller_loop_fused_batch_device(const pa_g1_affine *p, const pa_g2_affine 
  * lane-pair kernel's G2 steps use homogeneous coordinates and their own line
  * scaling; the final exponentiation removes any Fq2 factor, since
  * (q^12 - 1) / r is a multiple of q^2 - 1), so do not use them as Miller
- * values -- pa_miller_loop_fused_batch_device gives those. */
+ * values -- pa_miller_loop_fused_batch_device gives those.  The inputs may be
+ * any field elements: the Fq2-factor argument needs q[i] on E', so a pair
+ * whose q[i] is off the curve (neither point at infinity) holds the
+ * reference's own Miller value instead, recomputed on one lane by a launch
+ * behind the pairing-only kernel. */
 int pa_pairing_miller_loop_batch_device(const pa_g1_affine *p, const pa_g2_affine *q, pa_fq12 *out, size_t n,
                                         void *stream);
 /* final_exponentiation (mod.rs:104-160) on device records: one kernel launch

@@ -237,12 +237,28 @@ hipError_t mlp_launch(const uint64_t* p, const uint64_t* q, uint64_t* out, size_
 // fewer instructions (tools/pgen/kernels.py doubling_step_h); round 6: one lane
 // per pairing too (pa_gen_miller_loop1p).  The Miller-loop entries themselves
 // keep ml_launch.  PA_PAIRING_ML=ref: the reference-form kernels (A/B).
+//
+// Domain: the Fq2-factor argument needs Q on E' (doubling_step_h's tangent uses
+// b'); P is free, and so is the order of a curve point Q.  The reference's own
+// steps never use b, so for a Q off E' the two loops walk different curves and
+// no final exponentiation reconciles them.  pairing_gen_launch therefore puts
+// k_pairing_ml_fixup behind every pairing-only launch: it tests each Q against
+// E' exactly and recomputes the off-curve pairs in reference form, so every
+// e(P, Q) entry returns the reference's value for any field elements at every
+// batch size.  PA_PAIRING_FIXUP=0 leaves the launch out (A/B).
+hipError_t pairing_gen_launch(int lanes, const uint64_t* p, const uint64_t* q, uint64_t* out, size_t n,
+                              hipStream_t s) {
+    static const bool fixup = !(getenv("PA_PAIRING_FIXUP") && atoi(getenv("PA_PAIRING_FIXUP")) == 0);
+    hipError_t e = pa::launch_miller_loop_pairing_gen(lanes, p, q, out, n, s);
+    if (e == hipSuccess && fixup) e = pa::launch_pairing_ml_fixup(p, q, out, n, s);
+    return e;
+}
 hipError_t pairing_ml_launch(const uint64_t* p, const uint64_t* q, uint64_t* out, size_t n, hipStream_t s) {
     static const bool ref = getenv("PA_PAIRING_ML") && strcmp(getenv("PA_PAIRING_ML"), "ref") == 0;
     if (use_coop(n) || use_pq(n)) return ml_launch(p, q, out, n, s);
     if (const size_t h = split_head(n, s)) {
         TailFork* f = nullptr;
-        hipError_t e = pa::launch_miller_loop_pairing_gen(2, p, q, out, h, s);
+        hipError_t e = pairing_gen_launch(2, p, q, out, h, s);
         if (e == hipSuccess) e = tail_begin(s, &f);
         if (e == hipSuccess)
             e = tail_pq(n - h) ? pa::launch_pq_miller_loop(p + h * kG1Words, q + h * kG2Words, out + h * kF12Words, n - h,
@@ -253,7 +269,7 @@ hipError_t pairing_ml_launch(const uint64_t* p, const uint64_t* q, uint64_t* out
         return e != hipSuccess ? e : j;
     }
     if (ref) return pa::launch_miller_loop_gen(gen_lanes(n), p, q, out, n, s);
-    return pa::launch_miller_loop_pairing_gen(gen_lanes(n), p, q, out, n, s);
+    return pairing_gen_launch(gen_lanes(n), p, q, out, n, s);
 }
 hipError_t fe_launch(const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n, hipStream_t s) {
     if (use_pq(n)) return pa::launch_pq_final_exp(in, out, ok, n, s);

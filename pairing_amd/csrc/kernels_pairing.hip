@@ -67,6 +67,20 @@ __global__ void __launch_bounds__(64) k_miller_loop_prepared(const uint64_t* __r
     store12(out + 72 * i, f);
 }
 
+// Behind a pairing-only Miller loop (gen_launch.hip launch_miller_loop_pairing_gen):
+// one lane per pair tests its Q against E' and, off the curve, overwrites the
+// pair's value with the reference-form Miller value (pairing_fl.h
+// pairing_ml_fixup_lane).  A batch of curve points pays the test alone (Q's 200 B
+// record, P's infinity word and four Fq2 products per pair); a wave that holds an off-curve Q runs
+// that lane's serial Miller loop.  No host readback: stream-ordered, capturable.
+__global__ void __launch_bounds__(64) k_pairing_ml_fixup(const uint64_t* __restrict__ p_aff,
+                                                         const uint64_t* __restrict__ q_aff,
+                                                         uint64_t* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    pairing_ml_fixup_lane(p_aff, q_aff, out, i);
+}
+
 // ---- one G2Prepared shared by a batch of G1 points (lib.rs:88-96: the
 // caller passes the same &G2Prepared for every pair -- a verifying key's
 // prepared gamma / delta) ----
@@ -114,6 +128,12 @@ hipError_t launch_miller_loop_prepared(const uint64_t* p_aff, const uint64_t* pr
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_miller_loop_prepared, dim3(blocks_for(n, 64)), dim3(64), 0, stream, p_aff, prepared,
                        out, n);
+    return hipGetLastError();
+}
+hipError_t launch_pairing_ml_fixup(const uint64_t* p_aff, const uint64_t* q_aff, uint64_t* out, size_t n,
+                                   hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pairing_ml_fixup, dim3(blocks_for(n, 64)), dim3(64), 0, stream, p_aff, q_aff, out, n);
     return hipGetLastError();
 }
 hipError_t launch_shared_line_table(const uint64_t* prepared, uint32_t* table, hipStream_t stream) {

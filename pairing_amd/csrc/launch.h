@@ -86,6 +86,11 @@ hipError_t launch_miller_loop_shared_gen(const uint64_t* p_aff, const uint64_t* 
 // values up to Fq2 factors, which the final exponentiation removes
 hipError_t launch_miller_loop_pairing_gen(int lanes, const uint64_t* p_aff, const uint64_t* q_aff, uint64_t* out, size_t n,
                                           hipStream_t stream);
+// behind it, over the same pairs: a Q off E' (neither point at infinity) has its
+// value overwritten by the reference-form Miller value (kernels_pairing.hip
+// k_pairing_ml_fixup); the pairing-only steps use the curve constant
+hipError_t launch_pairing_ml_fixup(const uint64_t* p_aff, const uint64_t* q_aff, uint64_t* out, size_t n,
+                                   hipStream_t stream);
 // the generated Miller loop of (P_i, G2Prepared_i) pairs (tools/pgen
 // MillerLoopPreparedCfg): each lane reads its own record's lines
 hipError_t launch_miller_loop_prepared_gen(const uint64_t* p_aff, const uint64_t* prepared, uint64_t* out,

@@ -94,4 +94,45 @@ PA_DEV F12<1> ell_fl(const F12<1>& f, const uint64_t* rec, const F<1>& kx, const
     return mul_by_014(f, c, b, a);
 }
 
+// ell with the line still in registers (no G2Prepared record in memory)
+PA_DEV F12<1> ell_line_fl(const F12<1>& f, const LineFl& c, const F<1>& px, const F<1>& py) {
+    return mul_by_014(f, c.c2, mul_by_fq(c.c1, px), mul_by_fq(c.c0, py));
+}
+
+// y^2 == x^3 + 4 (1 + u), decided on canonical values (fl_is_zero), never on
+// lazy representatives
+PA_DEV bool g2_on_curve_fl(const F2<1>& x, const F2<1>& y) {
+    const F<4> b = dbl(dbl(fl_one()));
+    const F2<1> rhs = red(add(mul(sqr(x), x), F2<4>{b, b}));
+    const F2<3> d = sub(sqr(y), rhs);
+    return fl_is_zero(d.c0) && fl_is_zero(d.c1);
+}
+
+// The pairing-only Miller loops (tools/pgen/kernels.py doubling_step_h) use the
+// curve constant, so their value is the reference's up to an Fq2 factor only
+// for a Q on E'.  For pair i with Q off E' and neither point at infinity this
+// recomputes the reference's own Miller value (mod.rs:40-102: the loop of
+// k_g2_prepare fused with ell) and overwrites out[i]; every other pair is left
+// alone.  Returns whether it wrote.
+PA_DEV bool pairing_ml_fixup_lane(const uint64_t* __restrict__ p_aff, const uint64_t* __restrict__ q_aff,
+                                  uint64_t* __restrict__ out, size_t i) {
+    const uint64_t* pp = p_aff + 13 * i;
+    const uint64_t* qq = q_aff + 25 * i;
+    if ((pp[12] & 0xff) != 0 || (qq[24] & 0xff) != 0) return false;
+    const F2<1> qx = load2(qq), qy = load2(qq + 12);
+    if (g2_on_curve_fl(qx, qy)) return false;
+    const F<1> px = fl_load(pp), py = fl_load(pp + 6);
+    G2JacFl r{qx, qy, f2_one()};
+    F12<1> f = f12_one();
+#pragma unroll 1
+    for (int bit = 61; bit >= 0; bit--) {
+        f = ell_line_fl(f, dbl_step_fl(r), px, py);
+        if (((kBlsX >> 1) >> bit) & 1) f = ell_line_fl(f, add_step_fl(r, qx, qy), px, py);
+        f = sqr(f);
+    }
+    f = ell_line_fl(f, dbl_step_fl(r), px, py);
+    store12(out + 72 * i, red(conj(f)));
+    return true;
+}
+
 }  // namespace pa
