@@ -1,7 +1,7 @@
 // C ABI of pairing_amd (include/pairing_amd.h): argument checking, device
 // buffers for the host-pointer entry points, error reporting.  No compute
 // happens here; every entry point ends in a HIP kernel from
-// kernels_field.hip / kernels_pairing.hip.
+// the kernels_*.hip files or a generated code object (gen_launch.hip).
 #include <atomic>
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/pairing_amd.h"
+#include "env.h"
 #include "launch.h"
 #include "launch_msm.h"
 
@@ -54,20 +55,17 @@ thread_local std::string g_last_error;
 std::atomic<int> g_pairing_variant{0};
 int pairing_variant() { return g_pairing_variant.load(std::memory_order_relaxed); }
 
-size_t env_size(const char* name, size_t dflt) {
-    const char* e = getenv(name);   // A/B measurements
-    return e ? (size_t)strtoull(e, nullptr, 10) : dflt;
-}
+// the regime bounds: any count, for A/B measurements
 size_t coop_max() {
-    static const size_t v = env_size("PA_COOP_MAX", 2304);
+    static const size_t v = pa::env_count("PA_COOP_MAX", 2304);
     return v;
 }
 size_t pair_max() {
-    static const size_t v = env_size("PA_PAIR_MAX", 32768);
+    static const size_t v = pa::env_count("PA_PAIR_MAX", 32768);
     return v;
 }
 size_t one_max() {
-    static const size_t v = env_size("PA_ONE_MAX", 34048);
+    static const size_t v = pa::env_count("PA_ONE_MAX", 34048);
     return v;
 }
 // the same window's upper edge for the reference-form Miller loop alone (the
@@ -75,7 +73,7 @@ size_t one_max() {
 // its lane-pair kernel is slower than the pairing-only one, so one lane per pairing
 // wins up to 38912 pairs there (profiles/r05_regimes.txt)
 size_t ml_one_max() {
-    static const size_t v = env_size("PA_ML_ONE_MAX", 38912);
+    static const size_t v = pa::env_count("PA_ML_ONE_MAX", 38912);
     return v;
 }
 bool use_coop(size_t n) {
@@ -90,11 +88,11 @@ bool use_coop(size_t n) {
 // ~8.4 ms (4096: 6.45 vs 8.41, both kernels at two waves per SIMD above 2048);
 // profiles/r06_lane_groups.txt
 size_t pq_min() {
-    static const size_t v = env_size("PA_PQ_MIN", 768);
+    static const size_t v = pa::env_count("PA_PQ_MIN", 768);
     return v;
 }
 size_t pq_max() {
-    static const size_t v = env_size("PA_PQ_MAX", 4096);
+    static const size_t v = pa::env_count("PA_PQ_MAX", 4096);
     return v;
 }
 bool use_pq(size_t n) {
@@ -129,13 +127,13 @@ constexpr int kMaxWnafWindow = 62;
 // pairing-only Miller values differ from the cooperative Miller loop's by Fq2
 // factors, as pa_pairing_miller_loop_batch_device documents).  Not under
 // stream capture (the side stream would join the graph); PA_TAIL_MAX=0 turns
-// it off, PA_TAIL_SERIAL=1 runs the tail on the caller's stream (A/B).
+// it off.
 size_t tail_max() {
     // profiles/r06_tail/: the forked tail beats a second lane-pair wave (15.6-15.7
     // ms) up to ~2000 tail pairs: 32769 10.8 ms, 33024 10.6, 33792 13.1 (the
     // cooperative kernels), 34048 12.9, 34816 13.0 (the lane groups); 35840
     // 15.7 -- no better than no split
-    static const size_t v = env_size("PA_TAIL_MAX", 2048);
+    static const size_t v = pa::env_count("PA_TAIL_MAX", 2048);
     return v;
 }
 // the tail's kernels: the cooperative ones up to 832 tail pairings, the lane
@@ -164,12 +162,9 @@ size_t split_head(size_t n, hipStream_t s) {
     if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return 0;
     return pair_max();
 }
-// a fork whose side stream is ordered after everything enqueued on s (nullptr
-// with PA_TAIL_SERIAL: the tail runs on s)
+// a fork whose side stream is ordered after everything enqueued on s
 hipError_t tail_begin(hipStream_t s, TailFork** out) {
-    static const bool serial = getenv("PA_TAIL_SERIAL") && atoi(getenv("PA_TAIL_SERIAL")) != 0;
     *out = nullptr;
-    if (serial) return hipSuccess;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -222,21 +217,13 @@ hipError_t ml_launch(const uint64_t* p, const uint64_t* q, uint64_t* out, size_t
     if (use_coop(n)) return pa::launch_coop_miller_loop(p, q, out, n, s, coop_vm());
     return pa::launch_miller_loop_gen(gen_lanes(n, true), p, q, out, n, s);
 }
-// Miller loop of (P_i, G2Prepared_i) pairs: the generated kernel (tools/pgen
-// miller_loop_prepared_prog); PA_ML_PREPARED=hipcc selects round 4's HIP C++
-// kernel (kernels_pairing.hip) for A/B runs
-hipError_t mlp_launch(const uint64_t* p, const uint64_t* q, uint64_t* out, size_t n, hipStream_t s) {
-    static const bool hipcc = getenv("PA_ML_PREPARED") && strcmp(getenv("PA_ML_PREPARED"), "hipcc") == 0;
-    if (hipcc) return pa::launch_miller_loop_prepared(p, q, out, n, s);
-    return pa::launch_miller_loop_prepared_gen(p, q, out, n, s);
-}
 // The Miller loop in front of a final exponentiation (pa_pairing_batch[_device],
 // pa_multi_pairing_device): on lane pairs the pairing-only kernel, whose Miller
 // values differ from the reference's by Fq2 factors that the final
 // exponentiation removes ((q^12 - 1) / r is a multiple of q^2 - 1) -- 3.5 %
 // fewer instructions (tools/pgen/kernels.py doubling_step_h); round 6: one lane
 // per pairing too (pa_gen_miller_loop1p).  The Miller-loop entries themselves
-// keep ml_launch.  PA_PAIRING_ML=ref: the reference-form kernels (A/B).
+// keep ml_launch.
 //
 // Domain: the Fq2-factor argument needs Q on E' (doubling_step_h's tangent uses
 // b'); P is free, and so is the order of a curve point Q.  The reference's own
@@ -245,16 +232,14 @@ hipError_t mlp_launch(const uint64_t* p, const uint64_t* q, uint64_t* out, size_
 // k_pairing_ml_fixup behind every pairing-only launch: it tests each Q against
 // E' exactly and recomputes the off-curve pairs in reference form, so every
 // e(P, Q) entry returns the reference's value for any field elements at every
-// batch size.  PA_PAIRING_FIXUP=0 leaves the launch out (A/B).
+// batch size.
 hipError_t pairing_gen_launch(int lanes, const uint64_t* p, const uint64_t* q, uint64_t* out, size_t n,
                               hipStream_t s) {
-    static const bool fixup = !(getenv("PA_PAIRING_FIXUP") && atoi(getenv("PA_PAIRING_FIXUP")) == 0);
     hipError_t e = pa::launch_miller_loop_pairing_gen(lanes, p, q, out, n, s);
-    if (e == hipSuccess && fixup) e = pa::launch_pairing_ml_fixup(p, q, out, n, s);
+    if (e == hipSuccess) e = pa::launch_pairing_ml_fixup(p, q, out, n, s);
     return e;
 }
 hipError_t pairing_ml_launch(const uint64_t* p, const uint64_t* q, uint64_t* out, size_t n, hipStream_t s) {
-    static const bool ref = getenv("PA_PAIRING_ML") && strcmp(getenv("PA_PAIRING_ML"), "ref") == 0;
     if (use_coop(n) || use_pq(n)) return ml_launch(p, q, out, n, s);
     if (const size_t h = split_head(n, s)) {
         TailFork* f = nullptr;
@@ -262,13 +247,12 @@ hipError_t pairing_ml_launch(const uint64_t* p, const uint64_t* q, uint64_t* out
         if (e == hipSuccess) e = tail_begin(s, &f);
         if (e == hipSuccess)
             e = tail_pq(n - h) ? pa::launch_pq_miller_loop(p + h * kG1Words, q + h * kG2Words, out + h * kF12Words, n - h,
-                                                      f ? f->side : s)
+                                                      f->side)
                           : pa::launch_coop_miller_loop(p + h * kG1Words, q + h * kG2Words, out + h * kF12Words,
-                                                        n - h, f ? f->side : s, coop_vm());
+                                                        n - h, f->side, coop_vm());
         const hipError_t j = tail_end(s, f);
         return e != hipSuccess ? e : j;
     }
-    if (ref) return pa::launch_miller_loop_gen(gen_lanes(n), p, q, out, n, s);
     return pairing_gen_launch(gen_lanes(n), p, q, out, n, s);
 }
 hipError_t fe_launch(const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n, hipStream_t s) {
@@ -280,9 +264,9 @@ hipError_t fe_launch(const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n, h
         if (e == hipSuccess) e = tail_begin(s, &f);
         if (e == hipSuccess)
             e = tail_pq(n - h) ? pa::launch_pq_final_exp(in + h * kF12Words, out + h * kF12Words, ok ? ok + h : nullptr,
-                                                    n - h, f ? f->side : s)
+                                                    n - h, f->side)
                           : pa::launch_coop_final_exp(in + h * kF12Words, out + h * kF12Words, ok ? ok + h : nullptr,
-                                                      n - h, f ? f->side : s, coop_vm());
+                                                      n - h, f->side, coop_vm());
         const hipError_t j = tail_end(s, f);
         return e != hipSuccess ? e : j;
     }
@@ -657,7 +641,8 @@ int pa_miller_loop_batch(const pa_g1_affine* p, const pa_g2_prepared* q, pa_fq12
     if ((rc = upload(dp, p, sizeof(pa_g1_affine) * n)) || (rc = upload(dq, q, sizeof(pa_g2_prepared) * n)))
         return rc;
     PA_TRY(dout.alloc(576 * n), "device scratch");
-    PA_TRY(mlp_launch(dp.as<uint64_t>(), dq.as<uint64_t>(), dout.as<uint64_t>(), n, call_stream()),
+    PA_TRY(pa::launch_miller_loop_prepared_gen(dp.as<uint64_t>(), dq.as<uint64_t>(), dout.as<uint64_t>(), n,
+                                               call_stream()),
            "kernel launch");
     PA_TRY(call_sync(), "kernel execution");
     return download(out, dout, 576 * n);
@@ -695,7 +680,8 @@ int pa_multi_miller_loop(const pa_g1_affine* p, const pa_g2_prepared* q, size_t 
         return rc;
     PA_TRY(dwork.alloc(576 * n), "device scratch");
     PA_TRY(dout.alloc(576), "device scratch");
-    PA_TRY(mlp_launch(dp.as<uint64_t>(), dq.as<uint64_t>(), dwork.as<uint64_t>(), n, call_stream()),
+    PA_TRY(pa::launch_miller_loop_prepared_gen(dp.as<uint64_t>(), dq.as<uint64_t>(), dwork.as<uint64_t>(), n,
+                                               call_stream()),
            "kernel launch");
     PA_TRY(pa::launch_fq12_product(dwork.as<uint64_t>(), n, dout.as<uint64_t>(), call_stream()), "kernel launch");
     PA_TRY(call_sync(), "kernel execution");
@@ -794,11 +780,7 @@ int pa_pairing_batch(const pa_g1_affine* p, const pa_g2_affine* q, pa_fq12* out,
     // overlaps the DMA of piece j - 1 (in) / j + 1 (out): one caller at 2^16,
     // reused result buffer, 19.19 ms with 1 piece, 18.89 with 2, 18.84 with 4
     // (profiles/r03_host_boundary.txt).
-    static const size_t kPieces = [] {
-        const char* e = getenv("PA_PIPELINE_PIECES");
-        const long v = e ? strtol(e, nullptr, 10) : 2;
-        return (size_t)(v < 1 ? 1 : (v > 4 ? 4 : v));
-    }();
+    static const size_t kPieces = (size_t)pa::env_clamp("PA_PIPELINE_PIECES", 2, 1, 4);
     hipEvent_t* h2d = c->ev;        // [k]: chunk's inputs copied (pinned in[k] free again)
     hipEvent_t* done = c->ev + 2;   // [k]: chunk's kernels finished (device in[k], ml[k] free)
     hipEvent_t* d2h = c->ev + 4;    // [k * kPieces + j]: piece j of the chunk's results in pinned out[k]
@@ -1420,8 +1402,8 @@ int pa_g2_prepare_batch_device(const pa_g2_affine* q, pa_g2_prepared* out, size_
 int pa_miller_loop_batch_device(const pa_g1_affine* p, const pa_g2_prepared* q, pa_fq12* out, size_t n,
                                 void* stream) {
     if (n && (!p || !q || !out)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
-    PA_TRY(mlp_launch((const uint64_t*)p, (const uint64_t*)q, (uint64_t*)out, n,
-                                           (hipStream_t)stream),
+    PA_TRY(pa::launch_miller_loop_prepared_gen((const uint64_t*)p, (const uint64_t*)q, (uint64_t*)out, n,
+                                               (hipStream_t)stream),
            "kernel launch");
     return PA_OK;
 }

@@ -109,9 +109,12 @@ PA_DEV F<1> fl_from_lane(const F<1>& x, int src) {
     return r;
 }
 
-// jac_double_3lane (curve.h) on the lazy core: dbl-2009-l's seven products
-// in three dependent levels over lanes 0..2; every lane ends with the point.
-// Caller: z != 0.
+// dbl-2009-l (ec.rs:296-354) with its seven products spread over lanes 0..2 of
+// one wave in three dependent levels
+//   (A = X^2, B = Y^2, T = Y Z) -> (C = B^2, (X + B)^2, F = (3A)^2) -> E (D - X3)
+// so a doubling costs three product latencies instead of seven, for one-lane
+// serial chains.  Every lane of the wave calls it with the same point and ends
+// with the result, the same field values as fl_jac_double.  Caller: z != 0.
 PA_DEV void fl_jac_double_3lane(FlJac& p, int lane) {
     F<1> m = mul(lane == 0 ? p.x : p.y, lane == 0 ? p.x : (lane == 1 ? p.y : p.z));
     const F<1> a = fl_from_lane(m, 0), b = fl_from_lane(m, 1), t = fl_from_lane(m, 2);

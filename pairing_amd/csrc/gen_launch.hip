@@ -139,11 +139,8 @@ hipError_t load(GenDevice& d, int k) {
 size_t wave_bytes() {
     size_t b = 0;
     for (int k = 0; k < kKernels; k++) b = kWaveBytes[k] > b ? kWaveBytes[k] : b;
-    if (const char* e = getenv("PA_GEN_WS_SLOTS")) {
-        const size_t x = strtoull(e, nullptr, 10) * kSlotBytes;
-        b = x > b ? x : b;
-    }
-    return b;
+    const size_t x = (size_t)env_clamp("PA_GEN_WS_SLOTS", 0, 0, LLONG_MAX / (long long)kSlotBytes) * kSlotBytes;
+    return x > b ? x : b;
 }
 
 // A workspace of at least `need` bytes that no unfinished launch on another

@@ -541,8 +541,6 @@ hipError_t launch_g1_fixed_base(const uint64_t* base, const uint64_t* scalars, u
                 return e;
     }
     hipStream_t chain = side[dev][0], fill = side[dev][1], check = side[dev][2], mul = stream;
-    static const bool serial = getenv("PA_COMB_SERIAL") && atoi(getenv("PA_COMB_SERIAL")) != 0;
-    if (serial) chain = fill = check = stream;   // measurement only: every kernel in order on the caller's stream
     // window boundaries of the parts (PA_COMB_SPLIT, e.g. "5" or "2,7": the
     // first window of every part after the first); "5" (5 + 12 windows)
     // measured best of the even and two-part splits (profiles/r02_glv_comb.txt)

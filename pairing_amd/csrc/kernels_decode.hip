@@ -897,10 +897,7 @@ unsigned blocks_for(size_t n) { return (unsigned)((n + 63) / 64); }
 namespace {
 std::atomic<int> g_decode_variant{0};   // pa_set_decode_kernel (any host thread): 0 by batch size, 1 one lane per record, 2 quad groups
 size_t decode_quad_max() {
-    static const size_t v = [] {
-        const char* e = getenv("PA_DECODE_QUAD_MAX");
-        return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)8192;
-    }();
+    static const size_t v = env_count("PA_DECODE_QUAD_MAX", 8192);
     return v;
 }
 }  // namespace

@@ -14,48 +14,6 @@ namespace pa {
 __constant__ const uint64_t kFqR2[6] = {0xf4df1f341c341746ULL, 0x0a76e6a609d104f1ULL, 0x8de5476c4c95b6d5ULL,
                                         0x67eb88a9939d83c0ULL, 0x9a793e85b519952dULL, 0x11988fe592cae3aaULL};
 
-// Fq::mul_assign over a batch, fq.rs:909-960.  Grid-stride so one launch
-// covers any n with a chip-filling grid; PF = 1 software-pipelines the loop:
-// the next element's operands are loaded before the current multiply, so a
-// wave's loads overlap its own ~600-instruction multiply instead of every
-// wave alternating a memory phase and a compute phase in lockstep.
-template <int PF>
-__global__ void __launch_bounds__(256) k_fq_mul_batch(const uint64_t* __restrict__ a,
-                                                       const uint64_t* __restrict__ b,
-                                                       uint64_t* __restrict__ out, size_t n) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if constexpr (PF) {
-        if (i >= n) return;
-        Fq x, y;
-        fq_load(x, a + 6 * i);
-        fq_load(y, b + 6 * i);
-        for (;;) {
-            const size_t j = i + stride;
-            Fq xn, yn;
-            if (j < n) {
-                fq_load(xn, a + 6 * j);
-                fq_load(yn, b + 6 * j);
-            }
-            Fq z;
-            fq_mul(z, x, y);
-            fq_store(out + 6 * i, z);
-            if (j >= n) break;
-            x = xn;
-            y = yn;
-            i = j;
-        }
-    } else {
-        for (; i < n; i += stride) {
-            Fq x, y, z;
-            fq_load(x, a + 6 * i);
-            fq_load(y, b + 6 * i);
-            fq_mul(z, x, y);
-            fq_store(out + 6 * i, z);
-        }
-    }
-}
-
 // Field::pow, lib.rs:306-324: square-and-multiply over the exponent's bits,
 // most significant first (BitIterator, lib.rs:582-610); leading zeros square
 // one, so starting at the top set bit gives the same value.
@@ -142,31 +100,20 @@ __global__ void __launch_bounds__(256) k_fq_mul_batch_soa(const uint64_t* __rest
 #pragma unroll
     for (int j = 0; j < 6; j++) out[j * n + i] = (uint64_t)r.w[2 * j] | ((uint64_t)r.w[2 * j + 1] << 32);
 }
+// 27000 B of (unused) dynamic LDS per 256-thread block caps residency at
+// 5 waves per SIMD: fewer waves finish their multiplies together after the
+// last loads land (29.0 vs 30.0-30.3 us at 2^20; 3 waves: 32.2 us;
+// profiles/r02_fq_occupancy.txt).  PA_FQ_LDS overrides it for A/B runs.
+static unsigned fq_mul_lds() {
+    static const unsigned lds = (unsigned)env_clamp("PA_FQ_LDS", 27000, 0, UINT_MAX);
+    return lds;
+}
 hipError_t launch_fq_mul_batch_soa(const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    static const unsigned lds = [] {
-        const char* e = getenv("PA_FQ_LDS");
-        return e ? (unsigned)atoi(e) : 27000u;
-    }();
-    hipLaunchKernelGGL(k_fq_mul_batch_soa, dim3(blocks_for(n, 256)), dim3(256), lds, stream, a, b, out, n);
+    hipLaunchKernelGGL(k_fq_mul_batch_soa, dim3(blocks_for(n, 256)), dim3(256), fq_mul_lds(), stream, a, b, out, n);
     return hipGetLastError();
 }
 
-// Probe for config 2 (PA_FQ_VARIANT=9, not the product path): the same record
-// traffic with no multiply (z = x ^ y), i.e. the access-pattern bound: 25.0 us at
-// 2^20 against 29.0 us with the multiply (profiles/r02_fq_variants_s7.txt; a
-// wave-coalesced LDS-staged form of the multiply kernel measured 29.4-29.7 us).
-__global__ void __launch_bounds__(256) k_fq_xor_probe(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
-                                                       uint64_t* __restrict__ out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fq x, y;
-    fq_load(x, a + 6 * i);
-    fq_load(y, b + 6 * i);
-#pragma unroll
-    for (int k = 0; k < 12; k++) x.w[k] ^= y.w[k];
-    fq_store(out + 6 * i, x);
-}
 template <int OP>
 __global__ void __launch_bounds__(64) k_field_op(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
                                                  uint64_t* __restrict__ out, uint8_t* __restrict__ ok,
@@ -307,39 +254,12 @@ __global__ void __launch_bounds__(64) k_fq12_mul_by_014(const uint64_t* __restri
 hipError_t launch_fq_mul_batch(const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n,
                                hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    // Default: the lazy 28-bit core (k_fq_mul_batch_fl, 29.4 us at 2^20
-    // against 32.5 us for the 12 x u32 kernel, profiles/r02_fq_variants.txt;
-    // wave-coalesced LDS-DMA transfers measured 3 us slower in round 4,
-    // profiles/r04_fq_glds_icache.txt; nontemporal loads / stores 10 us slower,
-    // a grid-stride prefetching form 3-4 us slower, profiles/r04_fr_fq_ab.txt).
-    // PA_FQ_VARIANT=0 selects the 12 x u32 streaming kernel for A/B runs.
-    static const int variant = [] {
-        const char* e = getenv("PA_FQ_VARIANT");
-        return e ? atoi(e) : 4;
-    }();
-    if (variant == 9) {
-        hipLaunchKernelGGL(k_fq_xor_probe, dim3(blocks_for(n, 256)), dim3(256), 0, stream, a, b, out, n);
-        return hipGetLastError();
-    }
-    if (variant != 0) {
-        // 27000 B of (unused) dynamic LDS per 256-thread block caps residency at
-        // 5 waves per SIMD: fewer waves finish their multiplies together after the
-        // last loads land (29.0 vs 30.0-30.3 us at 2^20; 3 waves: 32.2 us;
-        // profiles/r02_fq_occupancy.txt).  PA_FQ_LDS overrides it for A/B runs.
-        static const unsigned lds = [] {
-            const char* e = getenv("PA_FQ_LDS");
-            return e ? (unsigned)atoi(e) : 27000u;
-        }();
-        hipLaunchKernelGGL(k_fq_mul_batch_fl, dim3(blocks_for(n, 256)), dim3(256), lds, stream, a, b, out, n);
-        return hipGetLastError();
-    }
-    size_t blocks = (n + 255) / 256;
-    const StreamCfg c = stream_cfg();
-    if (blocks > c.max_blocks) blocks = c.max_blocks;
-    if (c.prefetch)
-        hipLaunchKernelGGL(k_fq_mul_batch<1>, dim3((unsigned)blocks), dim3(256), 0, stream, a, b, out, n);
-    else
-        hipLaunchKernelGGL(k_fq_mul_batch<0>, dim3((unsigned)blocks), dim3(256), 0, stream, a, b, out, n);
+    // The lazy 28-bit core: 29.4 us at 2^20 against 32.5 us for the 12 x u32
+    // kernel it replaced (profiles/r02_fq_variants.txt); wave-coalesced LDS-DMA
+    // transfers measured 3 us slower in round 4 (profiles/r04_fq_glds_icache.txt),
+    // nontemporal loads / stores 10 us slower, a grid-stride prefetching form 3-4 us
+    // slower (profiles/r04_fr_fq_ab.txt).
+    hipLaunchKernelGGL(k_fq_mul_batch_fl, dim3(blocks_for(n, 256)), dim3(256), fq_mul_lds(), stream, a, b, out, n);
     return hipGetLastError();
 }
 

@@ -10,8 +10,8 @@
 namespace pa {
 
 // Field::mul_assign over a batch (fr.rs:438-465), grid-stride; PF = 1
-// prefetches the next element's operands before the current multiply (see
-// k_fq_mul_batch).
+// prefetches the next element's operands before the current multiply, so a
+// wave's loads overlap its own multiply.
 template <int PF>
 __global__ void __launch_bounds__(256) k_fr_mul_batch(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
                                                        uint64_t* __restrict__ out, size_t n) {
@@ -98,10 +98,7 @@ hipError_t launch_fr_mul_batch(const uint64_t* a, const uint64_t* b, uint64_t* o
     // waves per SIMD, as for config 2 (k_fq_mul_batch_fl): 21.2 vs 22.2-22.3 us
     // at 2^20 uncapped; nontemporal loads / stores were 1.5 us slower
     // (profiles/r04_fr_fq_ab.txt); PA_FR_LDS overrides it
-    static const unsigned lds = [] {
-        const char* e = getenv("PA_FR_LDS");
-        return e ? (unsigned)atoi(e) : 27000u;
-    }();
+    static const unsigned lds = (unsigned)env_clamp("PA_FR_LDS", 27000, 0, UINT_MAX);
     if (c.prefetch)
         hipLaunchKernelGGL(k_fr_mul_batch<1>, dim3((unsigned)blocks), dim3(256), lds, stream, a, b, out, n);
     else

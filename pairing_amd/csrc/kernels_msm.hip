@@ -22,14 +22,18 @@
 //      apart, zero digits are dropped.  Same order as a stable sort of the
 //      (w*B + |d|-1) keys, so the result is deterministic.
 //   3. k_msm_bucket_bounds: [start, end) per bucket from the sorted keys.
-//   4. k_msm_chunk_acc: one lane per 64 sorted items, mixed additions
-//      (madd-2007-bl) of the affine bases gathered from HBM (y negated for
-//      negative digits), run by run; k_msm_bucket_fix folds the pieces of
-//      buckets that span chunks and zeroes empty buckets.
-//   5. k_msm_segments: per window, sum_m m*B_m by running sums over segments of
-//      L buckets (T += B_m; S += T, top down), plus a*T for the segment offset.
-//   6. k_msm_group_sum (repeated): segment results -> one sum per window.
+//   4. k_msm_chunk_acc_fl / _fl2: one lane per 64 sorted items, mixed additions
+//      (madd-2007-bl) of the bases gathered from HBM as lazy rows (y negated
+//      for negative digits), run by run; k_msm_bucket_fix folds the pieces of
+//      buckets that span chunks and zeroes empty buckets (k_msm_long_fix: the
+//      buckets that span many).
+//   5. k_msm_segments_fl / _fl2: per window, sum_m m*B_m by running sums over
+//      segments of L buckets (T += B_m; S += T, top down), plus a*T for the
+//      segment offset.
+//   6. k_msm_group_sum_fl / _fl2 (repeated): segment results -> one sum per window.
 //   7. k_msm_horner_q: one group of lane quads, sum_w 2^(c*w) S_w.
+// Steps 4-6 run on the lazy 28-bit core for both groups (curve_fl.h, curve_fl2.h;
+// MsmKernels<G> names the group's kernels).
 // Steps 4-7 run per part of the windows (top windows first, msm_run): a part's
 // reduction (4's fix-up, 5, 6) and its Horner leg run on side streams while
 // the next part accumulates, so only the last part's tail is exposed.
@@ -55,6 +59,7 @@
 #include "curve_fl.h"
 #include "curve_fl2.h"
 #include "dec_quad.h"
+#include "env.h"
 #include "fr.h"
 #include "glv_split.h"
 #include "launch_msm.h"
@@ -141,11 +146,7 @@ static inline uint32_t msm_window_bits(size_t n) {
     int lg = 0;
     while (lg < 40 && ((size_t)1 << (lg + 1)) <= n) lg++;
     int c = lg - 3;
-    static const int cmax = [] {   // A/B knob: PA_MSM_CMAX (default 16)
-        const char* v = getenv("PA_MSM_CMAX");
-        const int k = v ? atoi(v) : 16;
-        return k < 4 ? 4 : (k > 20 ? 20 : k);
-    }();
+    static const int cmax = (int)env_clamp("PA_MSM_CMAX", 16, 4, 20);   // A/B knob
     if (c < 4) c = 4;
     if (c > cmax) c = cmax;
     return (uint32_t)c;
@@ -160,11 +161,7 @@ static inline uint32_t msm_window_bits(size_t n) {
 // from 2^21 virtual terms 17 (8 windows: 8 x 2^21 items against the plain
 // path's 17 x 2^20; 16 has 9 windows of 2^16 / 2 buckets, 6.75 ms against 6.03).
 static inline uint32_t msm_window_bits_glv(size_t nt) {
-    static const int env = [] {
-        const char* v = getenv("PA_MSM_GLV_C");
-        const int k = v ? atoi(v) : 0;
-        return k < 4 || k > 20 ? 0 : k;
-    }();
+    static const int env = (int)env_within("PA_MSM_GLV_C", 0, 4, 20);
     if (env) return (uint32_t)env;
     int lg = 0;
     while (lg < 40 && ((size_t)1 << (lg + 1)) <= nt) lg++;
@@ -184,11 +181,7 @@ static inline uint32_t msm_window_bits_glv(size_t nt) {
 // 2^18 terms, c = 12 / 13 / 14 / 15: 12.6 / 11.8 / 11.7 / 13.0 ms.  So the rule
 // is the single call's, which also makes a batch of one vector its job.
 static inline uint32_t msm_window_bits_batch(size_t nt) {
-    static const int env = [] {
-        const char* v = getenv("PA_MSM_BATCH_C");
-        const int k = v ? atoi(v) : 0;
-        return k < 4 || k > 20 ? 0 : k;
-    }();
+    static const int env = (int)env_within("PA_MSM_BATCH_C", 0, 4, 20);
     return env ? (uint32_t)env : msm_window_bits_glv(nt);
 }
 
@@ -202,11 +195,8 @@ constexpr uint32_t kMsmChunk = 64;
 // items, 320 waves at 64 per lane)
 constexpr size_t kMsmFillLanes = 65536;
 static uint32_t msm_chunk(size_t items, uint32_t parts) {
-    static const int env = [] {
-        const char* v = getenv("PA_MSM_CHUNK");
-        return v ? atoi(v) : 0;
-    }();
-    if (env) return (uint32_t)(env < 8 ? 8 : (env > 512 ? 512 : env));
+    static const int env = (int)env_clamp("PA_MSM_CHUNK", 0, -1, 512);   // 0: unset; else 8..512
+    if (env) return (uint32_t)(env < 8 ? 8 : env);
     const size_t t = (items + kMsmFillLanes * parts - 1) / (kMsmFillLanes * parts);
     return (uint32_t)(t < 8 ? 8 : (t > kMsmChunk ? kMsmChunk : t));
 }
@@ -230,11 +220,7 @@ constexpr size_t kMsmLongSpan = 128;
 // evenly filled bucket's span (msm_run), so that large MSMs whose every
 // bucket spans several chunks keep the one-lane fold.
 static size_t msm_long_span_glv() {
-    static const size_t v = [] {
-        const char* e = getenv("PA_MSM_GLV_LONGSPAN");
-        const long k = e ? atol(e) : 0;
-        return (size_t)(k >= 1 && k <= 4096 ? k : 8);
-    }();
+    static const size_t v = (size_t)env_within("PA_MSM_GLV_LONGSPAN", 8, 1, 4096);
     return v;
 }
 constexpr unsigned kMsmLongBlocks = 256;
@@ -248,11 +234,7 @@ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // caller's stream in order; 3 and 4 measured slower: the tails compete with the
 // next part's accumulation for SIMDs, profiles/r04_msm_parts.txt)
 static uint32_t msm_parts(uint32_t W) {
-    static const uint32_t parts = [] {
-        const char* v = getenv("PA_MSM_PARTS");
-        const int k = v ? atoi(v) : 2;
-        return (uint32_t)(k < 1 ? 1 : (k > (int)kMsmMaxParts ? (int)kMsmMaxParts : k));
-    }();
+    static const uint32_t parts = (uint32_t)env_clamp("PA_MSM_PARTS", 2, 1, kMsmMaxParts);
     return parts < W ? parts : W;
 }
 
@@ -264,11 +246,7 @@ static uint32_t msm_parts(uint32_t W) {
 // 16 vectors of 2^16 terms, 10.92 / 11.33 / 11.47 / 11.99 ms at 256 of 2^12 and
 // 11.35 / 11.85 / 12.76 / 15.57 ms at 8 of 2^18 (profiles/msm_prepared_batch/).
 static uint32_t msm_parts_batch(size_t k) {
-    static const uint32_t parts = [] {
-        const char* v = getenv("PA_MSM_BATCH_PARTS");
-        const int q = v ? atoi(v) : 1;
-        return (uint32_t)(q < 1 ? 1 : (q > (int)kMsmMaxParts ? (int)kMsmMaxParts : q));
-    }();
+    static const uint32_t parts = (uint32_t)env_clamp("PA_MSM_BATCH_PARTS", 1, 1, kMsmMaxParts);
     return parts < k ? parts : (uint32_t)k;
 }
 
@@ -287,12 +265,8 @@ static hipError_t msm_plan(MsmPlan& p, int group, size_t n, bool glv = false, bo
     // A/B knob: PA_MSM_SEG; default 8 buckets per segment for G1, 4 for G2 (G2
     // at 2^16 / 2^18: 5.91 / 9.13 ms with 8, 5.73 / 8.90 with 4; G1 at 2^20: 173
     // vs 163 M terms/s; profiles/r04_msm_g2_lazy.txt)
-    static const int seg_env = [] {
-        const char* v = getenv("PA_MSM_SEG");
-        const int k = v ? atoi(v) : 0;
-        return k == 2 || k == 4 || k == 8 || k == 16 || k == 32 ? k : 0;
-    }();
-    const uint32_t seg = seg_env ? (uint32_t)seg_env : (group == 1 ? 8u : 4u);
+    static const uint32_t seg_env = (uint32_t)env_within("PA_MSM_SEG", 0, 2, 32);   // a power of two, or ignored
+    const uint32_t seg = seg_env && !(seg_env & (seg_env - 1)) ? seg_env : (group == 1 ? 8u : 4u);
     p.L = p.B < seg ? p.B : seg;  // short segments: the running sums are a latency chain per lane
     p.items = p.WT * n;
     p.passes = (p.c - 1 + 7) / 8;
@@ -681,9 +655,6 @@ __global__ void __launch_bounds__(256) k_sort_scatter(const uint32_t* __restrict
 // whatever the digit distribution (a window whose digits crowd into few
 // buckets -- the top window of scalars < r -- no longer makes a few lanes
 // walk hundreds of terms).
-#ifndef PA_MSM_ACC_ATTR
-#define PA_MSM_ACC_ATTR
-#endif
 // chunk k0 + i of the window part [w0, w1): its items [k T, (k+1) T) clipped to
 // the part's items [jlo, jhi) of the sorted (window-compacted) array, k0 =
 // floor(jlo / T).  A window's items start with a new bucket, so a chunk
@@ -697,48 +668,6 @@ PA_DEV bool chunk_range(size_t i, const uint32_t* __restrict__ wpre, uint32_t w0
     if (j0 < jlo) j0 = jlo;
     if (j1 > jhi) j1 = jhi;
     return j0 < j1;
-}
-
-template <int G>
-PA_DEV void msm_flush(uint32_t key, const Jac<typename Grp<G>::F>& acc, size_t j0, size_t k,
-                      const uint32_t* __restrict__ start, uint64_t* __restrict__ buckets,
-                      uint64_t* __restrict__ cont) {
-    constexpr int JW = Grp<G>::JW;
-    if (start[key] >= j0) store_jac(buckets + (size_t)JW * key, acc);
-    else store_jac(cont + (size_t)JW * k, acc);
-}
-
-template <int G>
-__global__ void __launch_bounds__(64) k_msm_chunk_acc(const uint64_t* __restrict__ bases,
-                                                      const uint32_t* __restrict__ keys,
-                                                      const uint32_t* __restrict__ vals,
-                                                      const uint32_t* __restrict__ start,
-                                                      const uint32_t* __restrict__ wpre, uint32_t w0, uint32_t w1,
-                                                      uint32_t T, uint32_t sentinel, uint64_t* __restrict__ buckets,
-                                                      uint64_t* __restrict__ cont) {
-    using F = typename Grp<G>::F;
-    size_t k, j0, j1;
-    if (!chunk_range((size_t)blockIdx.x * blockDim.x + threadIdx.x, wpre, w0, w1, T, k, j0, j1)) return;
-    uint32_t cur = keys[j0];
-    if (cur >= sentinel) return;  // zero digits sort last
-    Jac<F> acc;
-    jac_zero(acc);
-#pragma unroll 1
-    for (size_t j = j0; j < j1; j++) {
-        const uint32_t key = keys[j];
-        if (key >= sentinel) break;
-        if (key != cur) {
-            msm_flush<G>(cur, acc, j0, k, start, buckets, cont);
-            jac_zero(acc);
-            cur = key;
-        }
-        const uint32_t v = vals[j];
-        Aff<F> p;
-        load_aff(p, bases + (size_t)Grp<G>::AW * (v & 0x7fffffffu));
-        if (v >> 31) neg(p.y, p.y);
-        jac_add_mixed(acc, p);
-    }
-    msm_flush<G>(cur, acc, j0, k, start, buckets, cont);
 }
 
 // G1 on the lazy 28-bit core: the affine bases converted once per MSM
@@ -806,17 +735,15 @@ PA_DEV void msm_flush_fl(uint32_t key, const FlJac& acc, bool untouched, size_t 
     }
 }
 
-// ... and k_msm_chunk_acc<1> with the lazy mixed addition (curve_fl.h);
-// bucket pieces leave in the ABI form the later phases read.  PREFETCH: the
-// next item's base is gathered while the current addition runs (the one-wave
-// kernel's latency hiding); without it the two-wave kernel's other wave hides
-// the gathers and the 28 registers go to the addition.
-template <bool PREFETCH>
+// ... and the bucket accumulation with the lazy mixed addition (curve_fl.h);
+// bucket pieces leave in the ABI form the later phases read.  One wave per SIMD
+// (256 VGPRs + 75 AGPRs): the next item's base is gathered while the current
+// addition runs (two waves per SIMD spilled 42-84 registers and measured 1-10 %
+// slower).
 PA_DEV void chunk_acc_fl_body(const uint32_t* __restrict__ basefl, const uint32_t* __restrict__ keys,
-                                              const uint32_t* __restrict__ vals, const uint32_t* __restrict__ start,
-                                              const uint32_t* __restrict__ wpre, uint32_t w0, uint32_t w1,
-                                              uint32_t T, uint32_t sentinel, uint64_t* __restrict__ buckets,
-                                              uint64_t* __restrict__ cont) {
+                              const uint32_t* __restrict__ vals, const uint32_t* __restrict__ start,
+                              const uint32_t* __restrict__ wpre, uint32_t w0, uint32_t w1, uint32_t T,
+                              uint32_t sentinel, uint64_t* __restrict__ buckets, uint64_t* __restrict__ cont) {
     size_t k, j0, j1;
     if (!chunk_range((size_t)blockIdx.x * blockDim.x + threadIdx.x, wpre, w0, w1, T, k, j0, j1)) return;
     uint32_t cur = keys[j0];
@@ -859,7 +786,7 @@ PA_DEV void chunk_acc_fl_body(const uint32_t* __restrict__ basefl, const uint32_
     fetch(j0 + 1, key1, v1);
     F<1> tx, ty;
     bool inf;
-    if (PREFETCH) gather(key0, v0, tx, ty, inf);
+    gather(key0, v0, tx, ty, inf);
 #pragma unroll 1
     for (size_t j = j0; j < j1; j++) {
         if (key0 >= sentinel) break;
@@ -867,8 +794,7 @@ PA_DEV void chunk_acc_fl_body(const uint32_t* __restrict__ basefl, const uint32_
         fetch(j + 2, key2, v2);
         F<1> nx, ny;
         bool ninf;
-        if (PREFETCH) gather(key1, v1, nx, ny, ninf);
-        else gather(key0, v0, tx, ty, inf);
+        gather(key1, v1, nx, ny, ninf);
         if (key0 != cur) {
             msm_flush_fl(cur, acc, untouched, j0, k, start, buckets, cont);
             untouched = true;
@@ -882,36 +808,25 @@ PA_DEV void chunk_acc_fl_body(const uint32_t* __restrict__ basefl, const uint32_
         v0 = v1;
         key1 = key2;
         v1 = v2;
-        if (PREFETCH) {
-            tx = nx;
-            ty = ny;
-            inf = ninf;
-        }
+        tx = nx;
+        ty = ny;
+        inf = ninf;
     }
     msm_flush_fl(cur, acc, untouched, j0, k, start, buckets, cont);
 }
-#define PA_CHUNK_ACC_FL_ARGS                                                                                   \
-    const uint32_t *__restrict__ basefl, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals, \
-        const uint32_t *__restrict__ start, const uint32_t *__restrict__ wpre, uint32_t w0, uint32_t w1,      \
-        uint32_t T, uint32_t sentinel, uint64_t *__restrict__ buckets, uint64_t *__restrict__ cont
-// one wave per SIMD (256 VGPRs + 75 AGPRs), the base prefetched
-__global__ void __launch_bounds__(64) PA_MSM_ACC_ATTR k_msm_chunk_acc_fl(PA_CHUNK_ACC_FL_ARGS) {
-    chunk_acc_fl_body<true>(basefl, keys, vals, start, wpre, w0, w1, T, sentinel, buckets, cont);
+__global__ void __launch_bounds__(64) k_msm_chunk_acc_fl(const uint32_t* __restrict__ basefl,
+                                                         const uint32_t* __restrict__ keys,
+                                                         const uint32_t* __restrict__ vals,
+                                                         const uint32_t* __restrict__ start,
+                                                         const uint32_t* __restrict__ wpre, uint32_t w0, uint32_t w1,
+                                                         uint32_t T, uint32_t sentinel,
+                                                         uint64_t* __restrict__ buckets, uint64_t* __restrict__ cont) {
+    chunk_acc_fl_body(basefl, keys, vals, start, wpre, w0, w1, T, sentinel, buckets, cont);
 }
-// two waves per SIMD (256 registers), the gathers hidden by the other wave
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-k_msm_chunk_acc_fl_2w(PA_CHUNK_ACC_FL_ARGS) {
-    chunk_acc_fl_body<false>(basefl, keys, vals, start, wpre, w0, w1, T, sentinel, buckets, cont);
-}
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-k_msm_chunk_acc_fl_2wp(PA_CHUNK_ACC_FL_ARGS) {
-    chunk_acc_fl_body<true>(basefl, keys, vals, start, wpre, w0, w1, T, sentinel, buckets, cont);
-}
-
 
 // One lane per bucket: empty buckets become the identity; a bucket spanning
 // several chunks adds the continuation pieces of the chunks after its first.
-template <int G, bool LAZY>
+template <int G>
 __global__ void __launch_bounds__(64) k_msm_bucket_fix(const uint32_t* __restrict__ start,
                                                        const uint32_t* __restrict__ end, size_t b0, size_t b1,
                                                        uint32_t T, const uint64_t* __restrict__ cont,
@@ -940,87 +855,17 @@ __global__ void __launch_bounds__(64) k_msm_bucket_fix(const uint32_t* __restric
 #pragma unroll 1
         for (size_t k = first + 1; k <= last; k++) fl_jac_add(acc, fl_load_jac(cont + (size_t)JW * k));
         fl_store_jac(buckets + (size_t)JW * b, acc);
-        return;
-    } else if constexpr (LAZY) {
+    } else {
         FlJac2 acc = fl2_load_jac(buckets + (size_t)JW * b);
 #pragma unroll 1
         for (size_t k = first + 1; k <= last; k++) fl2_jac_add(acc, fl2_load_jac(cont + (size_t)JW * k));
         fl2_store_jac(buckets + (size_t)JW * b, acc);
-        return;
     }
-    Jac<F> acc;
-    load_jac(acc, buckets + (size_t)JW * b);
-#pragma unroll 1
-    for (size_t k = first + 1; k <= last; k++) {
-        Jac<F> x;
-        load_jac(x, cont + (size_t)JW * k);
-        jac_add(acc, x);
-    }
-    store_jac(buckets + (size_t)JW * b, acc);
 }
 
-// One lane per segment of L buckets of one window: sum_m m * B_m over the segment.
-template <int G>
-__global__ void __launch_bounds__(64) k_msm_segments(const uint64_t* __restrict__ buckets, uint32_t B, uint32_t L,
-                                                     size_t t0, size_t t1, uint64_t* __restrict__ segs) {
-    using F = typename Grp<G>::F;
-    constexpr int JW = Grp<G>::JW;
-    const size_t t = t0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= t1) return;
-    const uint32_t spw = B / L;
-    const size_t w = t / spw;
-    const uint32_t j = (uint32_t)(t % spw);
-    const uint64_t* bw = buckets + (size_t)JW * (w * B);
-    Jac<F> T, S;
-    jac_zero(T);
-    jac_zero(S);
-#pragma unroll 1
-    for (uint32_t m = (j + 1) * L; m > j * L; m--) {  // magnitudes (j*L, (j+1)*L], top down
-        Jac<F> bk;
-        load_jac(bk, bw + (size_t)JW * (m - 1));
-        jac_add(T, bk);
-        jac_add(S, T);
-    }
-    const uint32_t a = j * L;  // S = sum (m - a) B_m; add a * T
-    if (a && !jac_is_zero(T)) {
-        Jac<F> aT;
-        jac_zero(aT);
-#pragma unroll 1
-        for (int bit = 31; bit >= 0; bit--) {
-            jac_double(aT);
-            if ((a >> bit) & 1) jac_add(aT, T);
-        }
-        jac_add(S, aT);
-    }
-    store_jac(segs + (size_t)JW * t, S);
-}
-
-// out[w*stride + g] = sum_{k<G} in[w*stride + g*G + k]  (indices < count), windows
-// [w0, w1); the fixed per-window stride keeps the window parts' levels apart
-template <int G>
-__global__ void __launch_bounds__(64) k_msm_group_sum(const uint64_t* __restrict__ in, uint32_t count,
-                                                      uint32_t group, uint32_t gpw, uint32_t w0, uint32_t w1,
-                                                      uint32_t stride, uint64_t* __restrict__ out) {
-    using F = typename Grp<G>::F;
-    constexpr int JW = Grp<G>::JW;
-    const size_t t = (size_t)w0 * gpw + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (size_t)w1 * gpw) return;
-    const size_t w = t / gpw;
-    const uint32_t g = (uint32_t)(t % gpw);
-    Jac<F> acc;
-    jac_zero(acc);
-#pragma unroll 1
-    for (uint32_t k = 0; k < group; k++) {
-        const uint32_t idx = g * group + k;
-        if (idx >= count) break;
-        Jac<F> x;
-        load_jac(x, in + (size_t)JW * (w * stride + idx));
-        jac_add(acc, x);
-    }
-    store_jac(out + (size_t)JW * (w * stride + g), acc);
-}
-
-// k_msm_group_sum<1> on the lazy core, one quad per output (fl_jac_add_q)
+// out[w*stride + g] = sum_{k<group} in[w*stride + g*group + k]  (indices < count),
+// windows [w0, w1); the fixed per-window stride keeps the window parts' levels
+// apart.  G1: one quad per output (fl_jac_add_q).
 __global__ void __launch_bounds__(64) k_msm_group_sum_fl(const uint64_t* __restrict__ in, uint32_t count,
                                                          uint32_t group, uint32_t gpw, uint32_t w0, uint32_t w1,
                                                          uint32_t stride, uint64_t* __restrict__ out) {
@@ -1041,48 +886,6 @@ __global__ void __launch_bounds__(64) k_msm_group_sum_fl(const uint64_t* __restr
         fl_jac_add_q(acc, fl_load_jac(in + (size_t)JW * (w * stride + idx)), q);
     }
     if (q == 0) fl_store_jac(out + (size_t)JW * (w * stride + g), acc);
-}
-
-template <int G>
-__global__ void __launch_bounds__(64) k_msm_horner(const uint64_t* __restrict__ wsum, uint32_t stride, uint32_t W,
-                                                   uint32_t c, uint64_t* __restrict__ out) {
-    using F = typename Grp<G>::F;
-    constexpr int JW = Grp<G>::JW;
-    // one wave; the doublings use three lanes (jac_double_3lane), every lane
-    // holds the same accumulator
-    if (blockIdx.x != 0) return;
-    const int lane = threadIdx.x;
-    Jac<F> acc;
-    load_jac(acc, wsum + (size_t)JW * stride * (W - 1));
-#pragma unroll 1
-    for (int w = (int)W - 2; w >= 0; w--) {
-#pragma unroll 1
-        for (uint32_t k = 0; k < c; k++) jac_double_3lane(acc, lane);
-        Jac<F> x;
-        load_jac(x, wsum + (size_t)JW * stride * w);
-        jac_add(acc, x);
-    }
-    if (lane == 0) store_jac(out, acc);
-}
-
-// G1 Horner entirely on the lazy core: doublings over three lanes
-// (fl_jac_double_3lane), window sums added with fl_jac_add.  #E(Fq) is odd,
-// so a nonzero accumulator never doubles to zero and a zero one is skipped.
-__global__ void __launch_bounds__(64) k_msm_horner_fl(const uint64_t* __restrict__ wsum, uint32_t stride, uint32_t W,
-                                                      uint32_t c, uint64_t* __restrict__ out) {
-    constexpr int JW = Grp<1>::JW;
-    if (blockIdx.x != 0) return;
-    const int lane = threadIdx.x;
-    FlJac acc = fl_load_jac(wsum + (size_t)JW * stride * (W - 1));
-#pragma unroll 1
-    for (int w = (int)W - 2; w >= 0; w--) {
-        if (!fl_is_zero(acc.z)) {
-#pragma unroll 1
-            for (uint32_t k = 0; k < c; k++) fl_jac_double_3lane(acc, lane);
-        }
-        fl_jac_add(acc, fl_load_jac(wsum + (size_t)JW * stride * w));
-    }
-    if (lane == 0) fl_store_jac(out, acc);
 }
 
 // Horner on a group of lane quads (dec_quad.h; G1: 4 quads, G2: 8 quads): each
@@ -1183,7 +986,9 @@ __global__ void __launch_bounds__(64) k_msm_horner_batch_q(const uint64_t* __res
     store_jac_q(out + (size_t)JW * j, acc, lane % L == 0);
 }
 
-// k_msm_segments<1> on the lazy core (same sums, same formulas)
+// One lane per segment of L buckets of one window: sum_m m * B_m over the
+// segment, by running sums top down (T += B_m; S += T) plus a * T for the
+// segment's offset a.
 __global__ void __launch_bounds__(64) k_msm_segments_fl(const uint64_t* __restrict__ buckets, uint32_t B, uint32_t L,
                                                         size_t t0, size_t t1, uint64_t* __restrict__ segs) {
     // one lane per segment: the kernel is throughput bound (4 k waves); a quad
@@ -1251,7 +1056,7 @@ PA_DEV void msm_flush_fl2(uint32_t key, const FlJac2& acc, bool untouched, size_
     }
 }
 
-// ... k_msm_chunk_acc<2> with the lazy mixed addition; the (key, value) pair
+// ... the bucket accumulation with the lazy mixed addition; the (key, value) pair
 // of the next item in flight while the current addition runs (a prefetched
 // 224-byte base would not fit beside the Fq2 temporaries)
 __global__ void __launch_bounds__(64) k_msm_chunk_acc_fl2(const uint32_t* __restrict__ basefl,
@@ -1302,7 +1107,7 @@ __global__ void __launch_bounds__(64) k_msm_chunk_acc_fl2(const uint32_t* __rest
     msm_flush_fl2(cur, acc, untouched, j0, k, start, buckets, cont);
 }
 
-// k_msm_segments<2> on the lazy core (same sums, same formulas)
+// k_msm_segments_fl over Fq2
 __global__ void __launch_bounds__(64) k_msm_segments_fl2(const uint64_t* __restrict__ buckets, uint32_t B, uint32_t L,
                                                          size_t t0, size_t t1, uint64_t* __restrict__ segs) {
     constexpr int JW = Grp<2>::JW;
@@ -1332,7 +1137,7 @@ __global__ void __launch_bounds__(64) k_msm_segments_fl2(const uint64_t* __restr
     fl2_store_jac(segs + (size_t)JW * t, S);
 }
 
-// k_msm_group_sum<2> on the lazy core, one lane per output
+// k_msm_group_sum_fl over Fq2, one lane per output
 __global__ void __launch_bounds__(64) k_msm_group_sum_fl2(const uint64_t* __restrict__ in, uint32_t count,
                                                           uint32_t group, uint32_t gpw, uint32_t w0, uint32_t w1,
                                                           uint32_t stride, uint64_t* __restrict__ out) {
@@ -1470,17 +1275,16 @@ static hipError_t msm_side_streams(hipStream_t caller, hipStream_t out[2]) {
     static hipStream_t side[64][2] = {};
     std::lock_guard<std::mutex> g(mu);
     // the side streams at the highest priority: a part's reduction waves are
-    // dispatched as the next part's accumulation frees SIMDs (PA_MSM_PRIO=0: default priority)
-    static const bool prio = !getenv("PA_MSM_PRIO") || atoi(getenv("PA_MSM_PRIO")) != 0;
+    // dispatched as the next part's accumulation frees SIMDs
     int lo = 0, hi = 0;
-    if (prio && (e = hipDeviceGetStreamPriorityRange(&lo, &hi)) != hipSuccess) return e;
+    if ((e = hipDeviceGetStreamPriorityRange(&lo, &hi)) != hipSuccess) return e;
     if (!side[dev][0] || !side[dev][1]) {
         // streams belong to the current device: create them on the caller's
         int cur = 0;
         if ((e = hipGetDevice(&cur)) != hipSuccess) return e;
         if (cur != dev && (e = hipSetDevice(dev)) != hipSuccess) return e;
         for (int k = 0; k < 2 && e == hipSuccess; k++)
-            if (!side[dev][k]) e = hipStreamCreateWithPriority(&side[dev][k], hipStreamNonBlocking, prio ? hi : lo);
+            if (!side[dev][k]) e = hipStreamCreateWithPriority(&side[dev][k], hipStreamNonBlocking, hi);
         if (cur != dev) (void)hipSetDevice(cur);
         if (e != hipSuccess) return e;
     }
@@ -1504,263 +1308,279 @@ struct MsmJob {
     bool mont = false;    // the scalar rows are Montgomery Fr (< r), not FrRepr
 };
 
-template <int G>
-static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_bytes, hipStream_t s) {
-    constexpr int JW = Grp<G>::JW;
-    if (job.vectors == 0) return hipSuccess;
-    if (job.terms == 0) {
-        hipLaunchKernelGGL(k_jac_zero_out<G>, dim3(msm_blocks(job.vectors, 64)), dim3(64), 0, s, out, job.vectors);
-        return hipGetLastError();
-    }
-    const uint64_t* bases = job.bases;
-    const size_t n = job.glv ? 2 * job.terms : job.terms;   // items per window
-    MsmPlan p;
-    hipError_t e = msm_plan(p, G, n, job.glv, job.rows == nullptr, job.vectors);
-    if (e != hipSuccess) return e;
-    if (ws_bytes < p.total || !ws) return hipErrorInvalidValue;
-    if (!p.fits || p.items > 0xffffffffull) return hipErrorInvalidValue;  // 32-bit item positions and keys
-    const uint32_t WT = (uint32_t)p.WT, sentinel = WT * p.B;
-    char* base = static_cast<char*>(ws);
-    uint32_t* keys_in = reinterpret_cast<uint32_t*>(base + p.off_keys_in);
-    uint32_t* keys_out = reinterpret_cast<uint32_t*>(base + p.off_keys_out);
-    uint32_t* vals_in = reinterpret_cast<uint32_t*>(base + p.off_vals_in);
-    uint32_t* vals_out = reinterpret_cast<uint32_t*>(base + p.off_vals_out);
-    uint32_t* start = reinterpret_cast<uint32_t*>(base + p.off_start);
-    uint32_t* end = reinterpret_cast<uint32_t*>(base + p.off_end);
-    uint64_t* buckets = reinterpret_cast<uint64_t*>(base + p.off_buckets);
-    uint64_t* segs = reinterpret_cast<uint64_t*>(base + p.off_segs);
-    uint64_t* tmp = reinterpret_cast<uint64_t*>(base + p.off_tmp);
-    const size_t nb = p.WT * p.B;
+// The group's kernels of steps 4-6 on the lazy core, and the lanes that
+// group_sum spends per output (G1: a quad)
+template <int G> struct MsmKernels;
+template <> struct MsmKernels<1> {
+    static constexpr auto bases_fl = k_msm_bases_fl;
+    static constexpr auto chunk_acc = k_msm_chunk_acc_fl;
+    static constexpr auto segments = k_msm_segments_fl;
+    static constexpr auto group_sum = k_msm_group_sum_fl;
+    static constexpr unsigned kGroupSumLanes = 4;
+};
+template <> struct MsmKernels<2> {
+    static constexpr auto bases_fl = k_msm_bases_fl2;
+    static constexpr auto chunk_acc = k_msm_chunk_acc_fl2;
+    static constexpr auto segments = k_msm_segments_fl2;
+    static constexpr auto group_sum = k_msm_group_sum_fl2;
+    static constexpr unsigned kGroupSumLanes = 1;
+};
 
+// segment sums -> one per window, two at a time: shallow chains, 2 additions per
+// level; a fan-in of 2 / 3 / 4 / 8 measured 141.6 / 140.2 / 138.1 / 133.5 M terms/s
+// at 2^20 (profiles/r02_msm_tuning.txt)
+constexpr uint32_t kMsmGroup = 2;
+
+// The plan's workspace as the stages address it.  keys / vals: the sorted items
+// (msm_sort_items); basefl: the lazy base rows, the job's prepared ones or the
+// workspace's own.
+struct MsmWs {
+    uint32_t *keys_in, *keys_out, *vals_in, *vals_out, *start, *end, *hist, *wtot, *wpre;
+    uint64_t *buckets, *segs, *tmp, *cont, *hacc;
+    uint32_t *long_list, *long_count;   // part q: its list at long_list + b0, its count at long_count[q]
+    uint32_t* own_basefl;
+    const uint32_t *keys, *vals, *basefl;
+};
+static MsmWs msm_ws(const MsmPlan& p, const MsmJob& job, void* ws) {
+    char* base = static_cast<char*>(ws);
+    auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(base + off); };
+    auto u64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(base + off); };
+    MsmWs w{};
+    w.keys_in = u32(p.off_keys_in);
+    w.keys_out = u32(p.off_keys_out);
+    w.vals_in = u32(p.off_vals_in);
+    w.vals_out = u32(p.off_vals_out);
+    w.start = u32(p.off_start);
+    w.end = u32(p.off_end);
+    w.hist = u32(p.off_hist);
+    w.wtot = u32(p.off_wtot);
+    w.wpre = u32(p.off_wpre);
+    w.buckets = u64(p.off_buckets);
+    w.segs = u64(p.off_segs);
+    w.tmp = u64(p.off_tmp);
+    w.cont = u64(p.off_cont);
+    w.hacc = u64(p.off_hacc);
+    w.long_list = u32(p.off_long);
+    w.long_count = w.long_list + p.WT * p.B;
+    w.own_basefl = u32(p.off_basefl);
+    w.basefl = job.rows ? job.rows : w.own_basefl;
+    return w;
+}
+
+// Steps 1-2: the digits of every window, then the bucketing sort, ping-pong
+// between the _in and _out arrays; the last destination's tail past the nonzero
+// items is set to sentinel keys first.  n: items per window.
+static hipError_t msm_sort_items(const MsmJob& job, const MsmPlan& p, size_t n, MsmWs& w, hipStream_t s) {
+    const uint32_t WT = (uint32_t)p.WT, sentinel = WT * p.B;
     if (job.glv)
         hipLaunchKernelGGL(k_msm_digits_glv, dim3(msm_blocks(job.terms * job.vectors, 256)), dim3(256), 0, s,
                            job.scalars, job.terms, job.vectors, job.mont, (uint32_t)job.row_off, p.c, p.W, p.B,
-                           sentinel, keys_in, vals_in);
+                           sentinel, w.keys_in, w.vals_in);
     else
         hipLaunchKernelGGL(k_msm_digits, dim3(msm_blocks(n * job.vectors, 256)), dim3(256), 0, s, job.scalars, n,
-                           job.vectors, job.mont, p.c, p.W, p.B, sentinel, keys_in, vals_in);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    // the bucketing sort: ping-pong between the _in and _out arrays; the last
-    // destination's tail past the nonzero items is set to sentinel keys first
-    uint32_t* hist = reinterpret_cast<uint32_t*>(base + p.off_hist);
-    uint32_t* wtot = reinterpret_cast<uint32_t*>(base + p.off_wtot);
-    uint32_t* wpre = reinterpret_cast<uint32_t*>(base + p.off_wpre);
-    uint32_t *ksrc = keys_in, *vsrc = vals_in, *kdst = keys_out, *vdst = vals_out;
-    if ((size_t)WT * p.tpw > 0x7fffffffull) return hipErrorInvalidValue;   // the sort's grid
+                           job.vectors, job.mont, p.c, p.W, p.B, sentinel, w.keys_in, w.vals_in);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    uint32_t *ksrc = w.keys_in, *vsrc = w.vals_in, *kdst = w.keys_out, *vdst = w.vals_out;
     const unsigned tiles = WT * p.tpw;
     for (uint32_t pass = 0; pass < p.passes; pass++) {
         const SortPass sp{8 * pass, p.B - 1, sentinel, p.tpw, pass == 0 ? 1u : 0u, n};
-        hipLaunchKernelGGL(k_sort_hist, dim3(tiles), dim3(256), 0, s, ksrc, wtot, wpre, sp, hist);
-        hipLaunchKernelGGL(k_sort_scan, dim3(WT), dim3(1024), 0, s, hist, p.tpw, wtot);
+        hipLaunchKernelGGL(k_sort_hist, dim3(tiles), dim3(256), 0, s, ksrc, w.wtot, w.wpre, sp, w.hist);
+        hipLaunchKernelGGL(k_sort_scan, dim3(WT), dim3(1024), 0, s, w.hist, p.tpw, w.wtot);
         if (pass == 0)   // the same totals after every pass
-            hipLaunchKernelGGL(k_sort_wprefix, dim3(1), dim3(WT <= 64 ? 64 : 1024), 0, s, wtot, WT, wpre);
+            hipLaunchKernelGGL(k_sort_wprefix, dim3(1), dim3(WT <= 64 ? 64 : 1024), 0, s, w.wtot, WT, w.wpre);
         if (pass + 1 == p.passes && (e = hipMemsetAsync(kdst, 0xff, 4 * p.items, s)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_sort_scatter, dim3(tiles), dim3(256), 0, s, ksrc, vsrc, hist, wtot, wpre, sp, kdst, vdst);
+        hipLaunchKernelGGL(k_sort_scatter, dim3(tiles), dim3(256), 0, s, ksrc, vsrc, w.hist, w.wtot, w.wpre, sp, kdst,
+                           vdst);
         std::swap(ksrc, kdst);
         std::swap(vsrc, vdst);
     }
-    keys_out = ksrc;  // the last pass's output
-    vals_out = vsrc;
-    if ((e = hipMemsetAsync(start, 0, 4 * nb, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(end, 0, 4 * nb, s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_msm_bucket_bounds, dim3(msm_blocks(p.items, 256)), dim3(256), 0, s, keys_out, p.items,
-                       sentinel, start, end);
-    uint64_t* cont = reinterpret_cast<uint64_t*>(base + p.off_cont);
-    uint64_t* hacc = reinterpret_cast<uint64_t*>(base + p.off_hacc);
-    const uint32_t* basefl = job.rows ? job.rows : reinterpret_cast<const uint32_t*>(base + p.off_basefl);
-    // G2 on the lazy core's Fq2 (round 4); PA_MSM_G2_LAZY=0: the 12-word kernels (A/B)
-    static const bool g2_lazy_env = !getenv("PA_MSM_G2_LAZY") || atoi(getenv("PA_MSM_G2_LAZY")) != 0;
-    const bool g2_lazy = G == 2 && g2_lazy_env;
-    if (job.rows) {
-        if (G != 1) return hipErrorInvalidValue;   // prepared rows are G1's
-    } else if constexpr (G == 1)
-        hipLaunchKernelGGL(k_msm_bases_fl, dim3(msm_blocks(n, 256)), dim3(256), 0, s, bases, n,
-                           reinterpret_cast<uint32_t*>(base + p.off_basefl));
-    else if (g2_lazy)
-        hipLaunchKernelGGL(k_msm_bases_fl2, dim3(msm_blocks(n, 256)), dim3(256), 0, s, bases, n,
-                           reinterpret_cast<uint32_t*>(base + p.off_basefl));
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const uint32_t spw = p.B / p.L;
-    // segment sums -> one per window, `group` at a time (ping-pong segs <-> tmp);
-    // every part takes the same number of levels, so the window sums of all of
-    // them land in the same buffer
-    // shallow chains: 2 additions per level, 2 / 3 / 4 / 8 measured 141.6 / 140.2 / 138.1 / 133.5 M
-    // terms/s at 2^20 (profiles/r02_msm_tuning.txt); PA_MSM_GROUP to A/B
-    static const uint32_t group = [] {
-        const char* v = getenv("PA_MSM_GROUP");
-        const int g = v ? atoi(v) : 2;
-        return (uint32_t)(g < 2 ? 2 : (g > 16 ? 16 : g));
-    }();
-    uint64_t* wsum = segs;
-    for (uint32_t count = spw; count > 1; count = (count + group - 1) / group) wsum = wsum == segs ? tmp : segs;
+    w.keys = ksrc;   // the last pass's output
+    w.vals = vsrc;
+    return hipSuccess;
+}
 
-    // the windows' throughput kernels of one part (windows [w0, w1))
-    // (the part's item range is on the device, wpre: lanes for the most it can hold)
-    // the G1 bucket accumulation's kernel: PA_MSM_ACC=0 one wave per SIMD with
-    // the base prefetch, 1 two waves without it, 2 two waves with it (A/B)
-    static const int acc_kind = [] {
-        const char* e = getenv("PA_MSM_ACC");
-        return e ? atoi(e) : 0;
-    }();
-    auto accumulate = [&](uint32_t w0, uint32_t w1, hipStream_t st) {
-        const size_t chunks = ((size_t)(w1 - w0) * n + p.T - 1) / p.T + 1;
-        if constexpr (G == 1)
-            hipLaunchKernelGGL(acc_kind == 1 ? k_msm_chunk_acc_fl_2w
-                                             : (acc_kind == 2 ? k_msm_chunk_acc_fl_2wp : k_msm_chunk_acc_fl),
-                               dim3(msm_blocks(chunks, 64)), dim3(64), 0, st, basefl, keys_out, vals_out, start, wpre,
-                               w0, w1, p.T, sentinel, buckets, cont);
-        else if (g2_lazy)
-            hipLaunchKernelGGL(k_msm_chunk_acc_fl2, dim3(msm_blocks(chunks, 64)), dim3(64), 0, st, basefl, keys_out,
-                               vals_out, start, wpre, w0, w1, p.T, sentinel, buckets, cont);
-        else
-            hipLaunchKernelGGL(k_msm_chunk_acc<G>, dim3(msm_blocks(chunks, 64)), dim3(64), 0, st, bases, keys_out,
-                               vals_out, start, wpre, w0, w1, p.T, sentinel, buckets, cont);
-        return hipGetLastError();
-    };
-    // ... and its bucket -> window-sum reduction
-    // (part q: long-bucket list at long_list + b0, its count at long_count[q])
-    uint32_t* long_list = reinterpret_cast<uint32_t*>(base + p.off_long);
-    uint32_t* long_count = long_list + nb;
-    const bool lazy = G == 1 || g2_lazy;
-    size_t long_span = kMsmLongSpan;
-    if (job.glv) {
-        const size_t even = 2 * (n / ((size_t)p.B * p.T) + 1);
-        long_span = msm_long_span_glv() > even ? msm_long_span_glv() : even;
+// Step 3, and the plain entries' bases converted to lazy rows
+template <int G>
+static hipError_t msm_bounds_and_bases(const MsmJob& job, const MsmPlan& p, size_t n, const MsmWs& w, hipStream_t s) {
+    const size_t nb = p.WT * p.B;
+    hipError_t e;
+    if ((e = hipMemsetAsync(w.start, 0, 4 * nb, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.end, 0, 4 * nb, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_msm_bucket_bounds, dim3(msm_blocks(p.items, 256)), dim3(256), 0, s, w.keys, p.items,
+                       (uint32_t)(p.WT * p.B), w.start, w.end);
+    if (!job.rows)
+        hipLaunchKernelGGL(MsmKernels<G>::bases_fl, dim3(msm_blocks(n, 256)), dim3(256), 0, s, job.bases, n,
+                           w.own_basefl);
+    return hipGetLastError();
+}
+
+// Steps 4-6 over the windows [w0, w1) of one part, as both schedulers launch them
+template <int G>
+struct MsmStages {
+    using K = MsmKernels<G>;
+    const MsmPlan& p;
+    const MsmWs& w;
+    size_t n;           // items per window
+    uint32_t sentinel, spw;
+    size_t long_span;   // chunks above which k_msm_long_fix folds a bucket
+    uint64_t* wsum;     // where the last group-sum level leaves the window sums
+
+    MsmStages(const MsmPlan& plan, const MsmWs& ws, size_t items_per_window, bool glv)
+        : p(plan), w(ws), n(items_per_window), sentinel((uint32_t)(plan.WT * plan.B)), spw(plan.B / plan.L),
+          long_span(kMsmLongSpan), wsum(ws.segs) {
+        if (glv) {
+            const size_t even = 2 * (n / ((size_t)p.B * p.T) + 1);
+            long_span = msm_long_span_glv() > even ? msm_long_span_glv() : even;
+        }
+        // every part takes the same number of levels (ping-pong segs <-> tmp), so
+        // the window sums of all of them land in the same buffer
+        for (uint32_t count = spw; count > 1; count = (count + kMsmGroup - 1) / kMsmGroup)
+            wsum = wsum == w.segs ? w.tmp : w.segs;
     }
-    // segment sums -> one per window, `group` at a time, windows [w0, w1)
-    auto group_levels = [&](uint32_t w0, uint32_t w1, hipStream_t st) {
-        uint64_t *src = segs, *dst = tmp;
+
+    // the part's item range is on the device (wpre): lanes for the most it can hold
+    hipError_t accumulate(uint32_t w0, uint32_t w1, hipStream_t st) const {
+        const size_t chunks = ((size_t)(w1 - w0) * n + p.T - 1) / p.T + 1;
+        hipLaunchKernelGGL(K::chunk_acc, dim3(msm_blocks(chunks, 64)), dim3(64), 0, st, w.basefl, w.keys, w.vals,
+                           w.start, w.wpre, w0, w1, p.T, sentinel, w.buckets, w.cont);
+        return hipGetLastError();
+    }
+
+    // buckets -> window sums; q: the part's slot for its long-bucket count
+    hipError_t reduce(uint32_t w0, uint32_t w1, uint32_t q, hipStream_t st) const {
+        const size_t b0 = (size_t)w0 * p.B, b1 = (size_t)w1 * p.B;
+        hipError_t r;
+        if ((r = hipMemsetAsync(w.long_count + q, 0, 4, st)) != hipSuccess) return r;
+        hipLaunchKernelGGL(k_msm_bucket_fix<G>, dim3(msm_blocks(b1 - b0, 64)), dim3(64), 0, st, w.start, w.end, b0, b1,
+                           p.T, w.cont, w.buckets, w.long_list + b0, w.long_count + q, long_span);
+        hipLaunchKernelGGL(k_msm_long_fix<G>, dim3(kMsmLongBlocks), dim3(LazyJac<G>::NT), 0, st, w.start, w.end, p.T,
+                           w.cont, w.buckets, w.long_list + b0, w.long_count + q);
+        const size_t t0 = (size_t)w0 * spw, t1 = (size_t)w1 * spw;
+        hipLaunchKernelGGL(K::segments, dim3(msm_blocks(t1 - t0, 64)), dim3(64), 0, st, w.buckets, p.B, p.L, t0, t1,
+                           w.segs);
+        uint64_t *src = w.segs, *dst = w.tmp;
         for (uint32_t count = spw; count > 1;) {
-            const uint32_t gpw = (count + group - 1) / group;
+            const uint32_t gpw = (count + kMsmGroup - 1) / kMsmGroup;
             const size_t outs = (size_t)(w1 - w0) * gpw;
-            if constexpr (G == 1)
-                hipLaunchKernelGGL(k_msm_group_sum_fl, dim3(msm_blocks(4 * outs, 64)), dim3(64), 0, st, src, count,
-                                   group, gpw, w0, w1, spw, dst);
-            else if (g2_lazy)
-                hipLaunchKernelGGL(k_msm_group_sum_fl2, dim3(msm_blocks(outs, 64)), dim3(64), 0, st, src, count,
-                                   group, gpw, w0, w1, spw, dst);
-            else
-                hipLaunchKernelGGL(k_msm_group_sum<G>, dim3(msm_blocks(outs, 64)), dim3(64), 0, st, src, count, group,
-                                   gpw, w0, w1, spw, dst);
+            hipLaunchKernelGGL(K::group_sum, dim3(msm_blocks(K::kGroupSumLanes * outs, 64)), dim3(64), 0, st, src,
+                               count, kMsmGroup, gpw, w0, w1, spw, dst);
             count = gpw;
             std::swap(src, dst);
         }
         return hipGetLastError();
-    };
-    auto reduce = [&](uint32_t w0, uint32_t w1, uint32_t q, hipStream_t st) {
-        const size_t b0 = (size_t)w0 * p.B, b1 = (size_t)w1 * p.B;
-        hipError_t r;
-        if (lazy && (r = hipMemsetAsync(long_count + q, 0, 4, st)) != hipSuccess) return r;
-        if (lazy)
-            hipLaunchKernelGGL((k_msm_bucket_fix<G, true>), dim3(msm_blocks(b1 - b0, 64)), dim3(64), 0, st, start, end,
-                               b0, b1, p.T, cont, buckets, long_list + b0, long_count + q, long_span);
-        else
-            hipLaunchKernelGGL((k_msm_bucket_fix<G, false>), dim3(msm_blocks(b1 - b0, 64)), dim3(64), 0, st, start,
-                               end, b0, b1, p.T, cont, buckets, nullptr, long_count + q, long_span);
-        if (lazy)
-            hipLaunchKernelGGL(k_msm_long_fix<G>, dim3(kMsmLongBlocks), dim3(LazyJac<G>::NT), 0, st, start, end, p.T,
-                               cont, buckets, long_list + b0, long_count + q);
-        const size_t t0 = (size_t)w0 * spw, t1 = (size_t)w1 * spw;
-        if constexpr (G == 1)
-            hipLaunchKernelGGL(k_msm_segments_fl, dim3(msm_blocks(t1 - t0, 64)), dim3(64), 0, st, buckets, p.B, p.L,
-                               t0, t1, segs);
-        else if (g2_lazy)
-            hipLaunchKernelGGL(k_msm_segments_fl2, dim3(msm_blocks(t1 - t0, 64)), dim3(64), 0, st, buckets, p.B,
-                               p.L, t0, t1, segs);
-        else
-            hipLaunchKernelGGL(k_msm_segments<G>, dim3(msm_blocks(t1 - t0, 64)), dim3(64), 0, st, buckets, p.B, p.L,
-                               t0, t1, segs);
-        return group_levels(w0, w1, st);
-    };
-
-    // A batch: parts are ranges of vectors, [v0, v1) = windows [v0 W, v1 W), so
-    // every vector's Horner chain completes inside its part (k_msm_horner_batch_q
-    // writes out + JW j) and nothing is carried between parts.  One part by
-    // default (msm_parts_batch).  With more, the caller's stream accumulates part
-    // after part; the reduction and Horner grid of every part but the last run
-    // behind it on the side streams, in turn.
-    if (job.vectors > 1) {
-        if constexpr (G != 1) return hipErrorInvalidValue;   // prepared G1 rows only
-        const size_t k = job.vectors;
-        const uint32_t parts = msm_parts_batch(k);
-        auto horner = [&](size_t v0, size_t v1, hipStream_t st) {
-            hipLaunchKernelGGL(k_msm_horner_batch_q, dim3(msm_blocks(v1 - v0, kHornerPerWave)), dim3(64), 0, st, wsum,
-                               spw, p.W, p.c, v0, v1, out);
-            return hipGetLastError();
-        };
-        if (parts == 1) {
-            if ((e = accumulate(0, WT, s)) != hipSuccess || (e = reduce(0, WT, 0, s)) != hipSuccess) return e;
-            return horner(0, k, s);
-        }
-        hipStream_t side[2];
-        if ((e = msm_side_streams(s, side)) != hipSuccess) return e;
-        hipEvent_t ev[2 * kMsmMaxParts] = {};   // ev[2q]: part q accumulated; ev[2q + 1]: its outputs written
-        int made = 0;
-        hipError_t err = hipSuccess;
-        auto ck = [&](hipError_t x) {
-            if (err == hipSuccess) err = x;
-            return err == hipSuccess;
-        };
-        for (; made < 2 * (int)(parts - 1); made++)
-            if (!ck(hipEventCreateWithFlags(&ev[made], hipEventDisableTiming))) break;
-        for (uint32_t q = 0; q < parts && err == hipSuccess; q++) {
-            const size_t v0 = k * q / parts, v1 = k * (q + 1) / parts;
-            const uint32_t w0 = (uint32_t)v0 * p.W, w1 = (uint32_t)v1 * p.W;
-            if (!ck(accumulate(w0, w1, s))) break;
-            if (q + 1 == parts) {
-                if (ck(reduce(w0, w1, q, s))) ck(horner(v0, v1, s));
-                break;
-            }
-            hipStream_t st = side[q & 1];
-            if (!ck(hipEventRecord(ev[2 * q], s)) || !ck(hipStreamWaitEvent(st, ev[2 * q], 0)) ||
-                !ck(reduce(w0, w1, q, st)) || !ck(horner(v0, v1, st)))
-                break;
-            ck(hipEventRecord(ev[2 * q + 1], st));
-        }
-        for (uint32_t q = 0; q + 1 < parts && err == hipSuccess; q++) ck(hipStreamWaitEvent(s, ev[2 * q + 1], 0));
-        if (err != hipSuccess)   // let what this call queued on the side streams drain (see below)
-            for (hipStream_t x : side) (void)hipStreamSynchronize(x);
-        for (int i = 0; i < made; i++) (void)hipEventDestroy(ev[i]);
-        return err;
     }
+};
 
-    // the round-3 one-wave Horner kernels (PA_MSM_HORNER=1: three-lane
-    // doublings, G1 on the lazy core) run the whole MSM as one part
-    static const bool horner_wave = getenv("PA_MSM_HORNER") && atoi(getenv("PA_MSM_HORNER")) == 1;
-    const uint32_t parts = horner_wave ? 1 : msm_parts(p.W);
-    if (parts == 1) {
-        if ((e = accumulate(0, p.W, s)) != hipSuccess || (e = reduce(0, p.W, 0, s)) != hipSuccess) return e;
-        if (!horner_wave)
-            hipLaunchKernelGGL(k_msm_horner_q<G>, dim3(1), dim3(64), 0, s, wsum, spw, (int)p.W, 0, p.c, nullptr, out);
-        else if constexpr (G == 1)
-            hipLaunchKernelGGL(k_msm_horner_fl, dim3(1), dim3(64), 0, s, wsum, spw, p.W, p.c, out);
-        else
-            hipLaunchKernelGGL(k_msm_horner<G>, dim3(1), dim3(64), 0, s, wsum, spw, p.W, p.c, out);
-        return hipGetLastError();
-    }
-    // Window parts, top windows first.  The caller's stream runs every part's
-    // bucket accumulation back to back; part q's reduction runs on a side
-    // stream behind it and its Horner leg (windows [w0, w1), continuing the
-    // part above) on a third, so the latency-bound tails (segment-sum levels,
-    // the 16 doublings per window of the Horner chain) of the upper parts
-    // hide under the next parts' accumulation.  Only the last part's reduction
-    // and Horner leg are exposed.  Same window sums, same Horner: same point.
-    hipStream_t side[2];
-    if ((e = msm_side_streams(s, side)) != hipSuccess) return e;
-    hipStream_t red_s = side[0], hor_s = side[1];
-    static const bool serial = getenv("PA_MSM_SERIAL") && atoi(getenv("PA_MSM_SERIAL")) != 0;
-    if (serial) red_s = hor_s = s;   // measurement / debugging: the parts in order on the caller's stream
+// The events of one scheduled call, the first error of its launch sequence, and
+// what a failed sequence owes the caller before it returns
+struct MsmEvents {
     hipEvent_t ev[2 * kMsmMaxParts + 1] = {};
     int made = 0;
     hipError_t err = hipSuccess;
-    auto ck = [&](hipError_t x) {
+
+    explicit MsmEvents(int count) {
+        for (; made < count; made++)
+            if (!ck(hipEventCreateWithFlags(&ev[made], hipEventDisableTiming))) break;
+    }
+    ~MsmEvents() {
+        for (int k = 0; k < made; k++) (void)hipEventDestroy(ev[k]);
+    }
+    MsmEvents(const MsmEvents&) = delete;
+    MsmEvents& operator=(const MsmEvents&) = delete;
+
+    // latches the first error; false from then on
+    bool ck(hipError_t x) {
         if (err == hipSuccess) err = x;
         return err == hipSuccess;
+    }
+    // After a failed launch sequence, let this call's work already queued on
+    // the side streams drain before the caller may release the workspace (an
+    // event recorded now waits for that work only, not for what other callers
+    // queue on the shared side streams later).  Returns the first error.
+    hipError_t finish(const hipStream_t (&side)[2]) {
+        if (err != hipSuccess)
+            for (hipStream_t x : side) {
+                hipEvent_t done = nullptr;
+                if (hipEventCreateWithFlags(&done, hipEventDisableTiming) == hipSuccess &&
+                    hipEventRecord(done, x) == hipSuccess)
+                    (void)hipEventSynchronize(done);
+                else
+                    (void)hipStreamSynchronize(x);
+                if (done) (void)hipEventDestroy(done);
+            }
+        return err;
+    }
+};
+
+// A batch: parts are ranges of vectors, [v0, v1) = windows [v0 W, v1 W), so
+// every vector's Horner chain completes inside its part (k_msm_horner_batch_q
+// writes out + JW j) and nothing is carried between parts.  One part by
+// default (msm_parts_batch).  With more, the caller's stream accumulates part
+// after part; the reduction and Horner grid of every part but the last run
+// behind it on the side streams, in turn.
+static hipError_t msm_schedule_batch(const MsmStages<1>& st, size_t k, uint64_t* out, hipStream_t s) {
+    const MsmPlan& p = st.p;
+    const uint32_t parts = msm_parts_batch(k);
+    auto horner = [&](size_t v0, size_t v1, hipStream_t hs) {
+        hipLaunchKernelGGL(k_msm_horner_batch_q, dim3(msm_blocks(v1 - v0, kHornerPerWave)), dim3(64), 0, hs, st.wsum,
+                           st.spw, p.W, p.c, v0, v1, out);
+        return hipGetLastError();
     };
-    const int nev = 2 * (int)parts + 1;
-    for (; made < nev; made++)
-        if (!ck(hipEventCreateWithFlags(&ev[made], hipEventDisableTiming))) break;
+    hipError_t e;
+    if (parts == 1) {
+        const uint32_t WT = (uint32_t)p.WT;
+        if ((e = st.accumulate(0, WT, s)) != hipSuccess || (e = st.reduce(0, WT, 0, s)) != hipSuccess) return e;
+        return horner(0, k, s);
+    }
+    hipStream_t side[2];
+    if ((e = msm_side_streams(s, side)) != hipSuccess) return e;
+    MsmEvents ev(2 * (int)(parts - 1));   // ev[2q]: part q accumulated; ev[2q + 1]: its outputs written
+    for (uint32_t q = 0; q < parts && ev.err == hipSuccess; q++) {
+        const size_t v0 = k * q / parts, v1 = k * (q + 1) / parts;
+        const uint32_t w0 = (uint32_t)v0 * p.W, w1 = (uint32_t)v1 * p.W;
+        if (!ev.ck(st.accumulate(w0, w1, s))) break;
+        if (q + 1 == parts) {
+            if (ev.ck(st.reduce(w0, w1, q, s))) ev.ck(horner(v0, v1, s));
+            break;
+        }
+        hipStream_t qs = side[q & 1];
+        if (!ev.ck(hipEventRecord(ev.ev[2 * q], s)) || !ev.ck(hipStreamWaitEvent(qs, ev.ev[2 * q], 0)) ||
+            !ev.ck(st.reduce(w0, w1, q, qs)) || !ev.ck(horner(v0, v1, qs)))
+            break;
+        ev.ck(hipEventRecord(ev.ev[2 * q + 1], qs));
+    }
+    for (uint32_t q = 0; q + 1 < parts && ev.err == hipSuccess; q++) ev.ck(hipStreamWaitEvent(s, ev.ev[2 * q + 1], 0));
+    return ev.finish(side);
+}
+
+// A single MSM: window parts, top windows first.  The caller's stream runs
+// every part's bucket accumulation back to back; part q's reduction runs on a
+// side stream behind it and its Horner leg (windows [w0, w1), continuing the
+// part above) on a third, so the latency-bound tails (segment-sum levels,
+// the 16 doublings per window of the Horner chain) of the upper parts
+// hide under the next parts' accumulation.  Only the last part's reduction
+// and Horner leg are exposed.  Same window sums, same Horner: same point.
+template <int G>
+static hipError_t msm_schedule_windows(const MsmStages<G>& st, uint64_t* out, hipStream_t s) {
+    constexpr int JW = Grp<G>::JW;
+    const MsmPlan& p = st.p;
+    const uint32_t parts = msm_parts(p.W);
+    auto horner = [&](uint32_t w0, uint32_t w1, const uint64_t* leg_in, uint64_t* leg_out, hipStream_t hs) {
+        hipLaunchKernelGGL(k_msm_horner_q<G>, dim3(1), dim3(64), 0, hs, st.wsum, st.spw, (int)w1, (int)w0, p.c, leg_in,
+                           leg_out);
+        return hipGetLastError();
+    };
+    hipError_t e;
+    if (parts == 1) {
+        if ((e = st.accumulate(0, p.W, s)) != hipSuccess || (e = st.reduce(0, p.W, 0, s)) != hipSuccess) return e;
+        return horner(0, p.W, nullptr, out, s);
+    }
+    hipStream_t side[2];
+    if ((e = msm_side_streams(s, side)) != hipSuccess) return e;
+    const hipStream_t red_s = side[0], hor_s = side[1];
     // ev[2q]: part q accumulated; ev[2q + 1]: part q reduced; ev[2 parts]: the upper Horner legs done
+    MsmEvents ev(2 * (int)parts + 1);
     // part q covers windows [wlo(q), wlo(q - 1)); PA_MSM_WLO="b0,b1,..." (descending
     // lower bounds, A/B of unequal parts) overrides the even split
     static const std::vector<uint32_t> wlo_env = [] {
@@ -1782,45 +1602,47 @@ static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_
         if (use_env && q + 1 < parts) return wlo_env[q];
         return q + 1 == parts ? 0u : (uint32_t)(((uint64_t)p.W * (parts - 1 - q)) / parts);
     };
-    for (uint32_t q = 0; q < parts && err == hipSuccess; q++) {
+    for (uint32_t q = 0; q < parts && ev.err == hipSuccess; q++) {
         const uint32_t w1 = q == 0 ? p.W : wlo(q - 1), w0 = wlo(q);
-        if (!ck(accumulate(w0, w1, s))) break;
-        uint64_t* leg_out = q + 1 == parts ? out : hacc + (size_t)JW * q;
-        const uint64_t* leg_in = q == 0 ? nullptr : hacc + (size_t)JW * (q - 1);
+        if (!ev.ck(st.accumulate(w0, w1, s))) break;
+        uint64_t* leg_out = q + 1 == parts ? out : st.w.hacc + (size_t)JW * q;
+        const uint64_t* leg_in = q == 0 ? nullptr : st.w.hacc + (size_t)JW * (q - 1);
         if (q + 1 == parts) {
-            if (!ck(reduce(w0, w1, q, s)) || !ck(hipStreamWaitEvent(s, ev[2 * parts], 0))) break;
-            hipLaunchKernelGGL(k_msm_horner_q<G>, dim3(1), dim3(64), 0, s, wsum, spw, (int)w1, (int)w0, p.c, leg_in,
-                               leg_out);
-            ck(hipGetLastError());
+            if (ev.ck(st.reduce(w0, w1, q, s)) && ev.ck(hipStreamWaitEvent(s, ev.ev[2 * parts], 0)))
+                ev.ck(horner(w0, w1, leg_in, leg_out, s));
             break;
         }
-        if (!ck(hipEventRecord(ev[2 * q], s)) || !ck(hipStreamWaitEvent(red_s, ev[2 * q], 0)) ||
-            !ck(reduce(w0, w1, q, red_s)) || !ck(hipEventRecord(ev[2 * q + 1], red_s)) ||
-            !ck(hipStreamWaitEvent(hor_s, ev[2 * q + 1], 0)))
+        if (!ev.ck(hipEventRecord(ev.ev[2 * q], s)) || !ev.ck(hipStreamWaitEvent(red_s, ev.ev[2 * q], 0)) ||
+            !ev.ck(st.reduce(w0, w1, q, red_s)) || !ev.ck(hipEventRecord(ev.ev[2 * q + 1], red_s)) ||
+            !ev.ck(hipStreamWaitEvent(hor_s, ev.ev[2 * q + 1], 0)) || !ev.ck(horner(w0, w1, leg_in, leg_out, hor_s)))
             break;
-        hipLaunchKernelGGL(k_msm_horner_q<G>, dim3(1), dim3(64), 0, hor_s, wsum, spw, (int)w1, (int)w0, p.c, leg_in,
-                           leg_out);
-        if (!ck(hipGetLastError())) break;
-        if (q + 2 == parts) ck(hipEventRecord(ev[2 * parts], hor_s));
+        if (q + 2 == parts) ev.ck(hipEventRecord(ev.ev[2 * parts], hor_s));
     }
-    if (err != hipSuccess) {
-        // a failed launch sequence: let this call's work already queued on the
-        // side streams drain before the caller may release the workspace (an
-        // event recorded now waits for that work only, not for what other
-        // callers queue on the shared side streams later)
-        for (hipStream_t x : {red_s, hor_s}) {
-            hipEvent_t done = nullptr;
-            if (hipEventCreateWithFlags(&done, hipEventDisableTiming) == hipSuccess &&
-                hipEventRecord(done, x) == hipSuccess)
-                (void)hipEventSynchronize(done);
-            else
-                (void)hipStreamSynchronize(x);
-            if (done) (void)hipEventDestroy(done);
-        }
+    return ev.finish(side);
+}
+
+template <int G>
+static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_bytes, hipStream_t s) {
+    if (job.vectors == 0) return hipSuccess;
+    if (G != 1 && (job.rows || job.vectors > 1)) return hipErrorInvalidValue;   // prepared rows and batches are G1's
+    if (job.terms == 0) {
+        hipLaunchKernelGGL(k_jac_zero_out<G>, dim3(msm_blocks(job.vectors, 64)), dim3(64), 0, s, out, job.vectors);
+        return hipGetLastError();
     }
-    for (int k = 0; k < made; k++) (void)hipEventDestroy(ev[k]);
-    (void)JW;
-    return err;
+    const size_t n = job.glv ? 2 * job.terms : job.terms;   // items per window
+    MsmPlan p;
+    hipError_t e = msm_plan(p, G, n, job.glv, job.rows == nullptr, job.vectors);
+    if (e != hipSuccess) return e;
+    if (ws_bytes < p.total || !ws) return hipErrorInvalidValue;
+    if (!p.fits || p.items > 0xffffffffull) return hipErrorInvalidValue;  // 32-bit item positions and keys
+    if (p.WT * p.tpw > 0x7fffffffull) return hipErrorInvalidValue;        // the sort's grid
+    MsmWs w = msm_ws(p, job, ws);
+    if ((e = msm_sort_items(job, p, n, w, s)) != hipSuccess) return e;
+    if ((e = msm_bounds_and_bases<G>(job, p, n, w, s)) != hipSuccess) return e;
+    const MsmStages<G> st(p, w, n, job.glv);
+    if constexpr (G == 1)
+        if (job.vectors > 1) return msm_schedule_batch(st, job.vectors, out, s);
+    return msm_schedule_windows<G>(st, out, s);
 }
 
 hipError_t launch_msm(int group, const uint64_t* bases, const uint64_t* scalars, size_t n, uint64_t* out, void* ws,

@@ -1,10 +1,11 @@
-// Materialized-G2Prepared pairing kernels, one pairing per lane on the lazy
-// 28-bit core (pairing_fl.h; the fused Miller loop and final exponentiation
-// of the hot path are the generated code objects of tools/pgen, gen_launch.hip).
+// G2Prepared and Miller-value kernels, one item per lane on the lazy 28-bit
+// core (pairing_fl.h; the Miller loops and final exponentiations of the hot
+// path are the generated code objects of tools/pgen, gen_launch.hip).
 //
 //   k_g2_prepare             G2Prepared::from_affine  (mod.rs:168-358)
-//   k_miller_loop_prepared   miller_loop([(p, q_prepared)])  (mod.rs:40-102)
-//   k_fq12_product           Fq12 tree product (multi-pair miller_loop)
+//   k_pairing_ml_fixup       reference-form Miller value of a pair whose Q is off E'
+//   k_shared_line_table      one G2Prepared -> the shared Miller loop's line table
+//   k_fq12_product_level     Fq12 tree product (multi-pair miller_loop)
 //
 // HBM records use the reference's in-memory order (include/pairing_amd.h).
 #include "launch.h"
@@ -12,7 +13,6 @@
 
 namespace pa {
 
-constexpr int kAffG1Words = 13;  // {x, y, infinity+pad}
 constexpr int kAffG2Words = 25;
 constexpr int kPreparedWords = kNumCoeffs * 36 + 1;
 
@@ -39,32 +39,6 @@ __global__ void __launch_bounds__(64) k_g2_prepare(const uint64_t* __restrict__ 
         for (int w = 0; w < kNumCoeffs * 36; w++) dst[w] = 0;
     }
     dst[kNumCoeffs * 36] = qinf ? 1ull : 0ull;
-}
-
-// miller_loop over one (G1Affine, G2Prepared) pair per lane on the lazy core
-__global__ void __launch_bounds__(64) k_miller_loop_prepared(const uint64_t* __restrict__ p_aff,
-                                                             const uint64_t* __restrict__ prepared,
-                                                             uint64_t* __restrict__ out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t* pp = p_aff + kAffG1Words * i;
-    const bool pinf = (pp[12] & 0xff) != 0;
-    const F<1> kx = mul(fl_load(pp), fl_c(FL_TO));
-    const F<1> ky = mul(fl_load(pp + 6), fl_c(FL_TO));
-    const uint64_t* src = prepared + kPreparedWords * i;
-    const bool qinf = (src[kNumCoeffs * 36] & 0xff) != 0;
-    F12<1> f = f12_one();
-    int k = 0;
-#pragma unroll 1
-    for (int bit = 61; bit >= 0; bit--) {
-        f = ell_fl(f, src + 36 * k++, kx, ky);
-        if (((kBlsX >> 1) >> bit) & 1) f = ell_fl(f, src + 36 * k++, kx, ky);
-        f = sqr(f);
-    }
-    f = ell_fl(f, src + 36 * k, kx, ky);
-    f = red(conj(f));
-    if (pinf || qinf) f = f12_one();
-    store12(out + 72 * i, f);
 }
 
 // Behind a pairing-only Miller loop (gen_launch.hip launch_miller_loop_pairing_gen):
@@ -121,13 +95,6 @@ static inline unsigned blocks_for(size_t n, unsigned bs) { return (unsigned)((n 
 hipError_t launch_g2_prepare(const uint64_t* q_aff, uint64_t* prepared, size_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_g2_prepare, dim3(blocks_for(n, 64)), dim3(64), 0, stream, q_aff, prepared, n);
-    return hipGetLastError();
-}
-hipError_t launch_miller_loop_prepared(const uint64_t* p_aff, const uint64_t* prepared, uint64_t* out,
-                                       size_t n, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_miller_loop_prepared, dim3(blocks_for(n, 64)), dim3(64), 0, stream, p_aff, prepared,
-                       out, n);
     return hipGetLastError();
 }
 hipError_t launch_pairing_ml_fixup(const uint64_t* p_aff, const uint64_t* q_aff, uint64_t* out, size_t n,

@@ -94,11 +94,7 @@ static inline unsigned blocks_for(size_t n, unsigned bs) { return (unsigned)((n 
 // product pays a level for nothing (0.26 against 0.20 ms).
 // PA_SEGPROD_SERIAL_MAX overrides (A/B measurements).
 size_t segprod_serial_max() {
-    static const size_t v = [] {
-        const char* e = getenv("PA_SEGPROD_SERIAL_MAX");
-        const size_t c = e ? (size_t)strtoull(e, nullptr, 10) : 4;
-        return c ? c : 1;
-    }();
+    static const size_t v = (size_t)env_clamp("PA_SEGPROD_SERIAL_MAX", 4, 1, LLONG_MAX);
     return v;
 }
 

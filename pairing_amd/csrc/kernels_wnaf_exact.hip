@@ -17,11 +17,14 @@
 //   formula's outputs represent T_k = (2k+1) B and field values are canonical.
 //   So the chain is rebuilt in parallel:
 //     k_wx_prep     D (the reference's doubling), x_D, 2 Z_D^3         (1 lane)
-//     k_wx_affine   affine (2k+1) B per lane (any addition chain)
+//     k_wx_affine_fl  affine (2k+1) B per lane (any addition chain)
 //     k_wx_coef     C_0 = Z_B, C_k = c_k
-//     k_wx_scan     log2(N) steps C_i <- C_i * C_(i-2^s)^(3^(2^s)): after
+//     k_wx_scan_q1 / k_wx_scan_fl2 (G1 / G2)
+//                   log2(N) steps C_i <- C_i * C_(i-2^s)^(3^(2^s)): after
 //                   the last step C_k = Z_k (a Hillis-Steele scan over the
-//                   maps z -> c z^(3^e); exponents: wnaf_exact_consts.h)
+//                   maps z -> c z^(3^e); exponents: wnaf_exact_consts.h);
+//                   k_wx_scan4_fl1: two of G1's steps in one launch where
+//                   both exponents are full size
 //     k_wx_finish   T_k = (x_k Z_k^2, y_k Z_k^3, Z_k), T_0 = B's own words
 //   The closed form needs the generic branch of every addition (T_(k-1) and
 //   D nonzero, x_(k-1) != x_D).  A base for which some step is special (zero,
@@ -34,10 +37,12 @@
 //                        packed digit-major column, then wnaf_exp on the lazy
 //                        core (curve_fl.h / curve_fl2.h: dbl-2009-l and
 //                        add-2007-bl with the reference's field-value
-//                        sequence), the coordinates canonical at the store --
-//                        the same Jacobian words as the 12-word kernel
-//                        (k_wx_fixed_base_mul, PA_WX_MUL=word12 for A/B)
-#include <cstring>
+//                        sequence), the coordinates canonical at the store:
+//                        the Jacobian words of wnaf_exp on the 12-word core
+//   k_wx_digit_keys      + a radix sort: the order in which the multiply's
+//                        lanes take the scalars (not above 2^31 - 1 scalars)
+// The fixed-scalar path and the serial replay run on the 12-word core (curve.h).
+#include <utility>
 
 #include <hipcub/hipcub.hpp>
 
@@ -306,33 +311,10 @@ __global__ void __launch_bounds__(64) k_wx_prep(const uint64_t* __restrict__ bas
     meta[5 * W + 1] = on_curve ? 1 : 0;
 }
 
-// affine (2k + 1) B for k < N (a plain double-and-add: affine values do not
-// depend on the chain)
-template <int G>
-__global__ void __launch_bounds__(64) k_wx_affine(const uint64_t* __restrict__ base, size_t N,
-                                                  uint64_t* __restrict__ aff, uint64_t* __restrict__ meta) {
-    using F = typename Wx<G>::F;
-    constexpr int W = Wx<G>::W;
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= N) return;
-    Jac<F> b, r;
-    load_jac(b, base);
-    const uint64_t m = 2 * (uint64_t)k + 1;
-    r = b;
-    for (int bit = 62 - __builtin_clzll(m); bit >= 0; bit--) {
-        jac_double(r);
-        if ((m >> bit) & 1) jac_add(r, b);
-    }
-    Aff<F> a;
-    jac_to_affine(a, r);
-    if (a.inf) meta[5 * W] = 1;
-    store(aff + (size_t)2 * W * k, a.x);
-    store(aff + (size_t)2 * W * k + W, a.y);
-}
-
-// the same affine multiples on the lazy core (curve_fl.h / curve_fl2.h), the
-// inversion of z by the 12-word binary GCD (bgcd.h); the affine values do not
-// depend on the chain, so any exact group law gives the same words
+// affine (2k + 1) B for k < N by a plain double-and-add on the lazy core
+// (curve_fl.h / curve_fl2.h), the inversion of z by the 12-word binary GCD
+// (bgcd.h); the affine values do not depend on the chain, so any exact group
+// law gives the same words
 PA_DEV bool wl_inverse(F<1>& r, const F<1>& a) {
     Fq t;
     const bool ok = fq_inv(t, fl_to_abi(a));
@@ -402,54 +384,6 @@ PA_DEV int top_bit(const uint64_t* e) {
         if (e[w]) return 64 * w + 63 - __builtin_clzll(e[w]);
     return -1;
 }
-PA_DEV void pow3(Fq& r, const Fq& z, int s) {
-    const uint64_t* e = PA_WX_E1[s];
-    one(r);
-    for (int b = top_bit(e); b >= 0; b--) {
-        sqr(r, r);
-        if ((e[b >> 6] >> (b & 63)) & 1) mul(r, r, z);
-    }
-}
-PA_DEV void pow3(Fq2& r, const Fq2& z, int s) {
-    // z^(e0 + e1 q) = z^e0 conj(z)^e1 (q = 3 mod 4: z^q = conj(z)), one run of squarings
-    const uint64_t* e0 = PA_WX_E2[s][0];
-    const uint64_t* e1 = PA_WX_E2[s][1];
-    Fq2 zc, zz;
-    zc.c0 = z.c0;
-    neg(zc.c1, z.c1);
-    mul(zz, z, zc);
-    one(r);
-    const int t0 = top_bit(e0), t1 = top_bit(e1);
-    for (int b = t0 > t1 ? t0 : t1; b >= 0; b--) {
-        sqr(r, r);
-        const bool x0 = (e0[b >> 6] >> (b & 63)) & 1, x1 = (e1[b >> 6] >> (b & 63)) & 1;
-        if (x0 && x1)
-            mul(r, r, zz);
-        else if (x0)
-            mul(r, r, z);
-        else if (x1)
-            mul(r, r, zc);
-    }
-}
-
-template <int G>
-__global__ void __launch_bounds__(64) k_wx_scan(const uint64_t* __restrict__ cin, uint64_t* __restrict__ cout,
-                                                size_t N, size_t off, int s, const uint64_t* __restrict__ meta) {
-    using F = typename Wx<G>::F;
-    constexpr int W = Wx<G>::W;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N || meta[5 * W]) return;
-    F v;
-    load(v, cin + (size_t)W * i);
-    if (i >= off) {
-        F p, t;
-        load(p, cin + (size_t)W * (i - off));
-        pow3(t, p, s);
-        mul(v, v, t);
-    }
-    store(cout + (size_t)W * i, v);
-}
-
 // The scan step on the lazy core.  G1: one element per lane QUAD, its
 // exponentiation spread over the quad (dec_quad.h: a dependent product is ~0.6
 // us instead of ~1.6 us on the 12-word core), a 4-bit sliding window over the
@@ -479,24 +413,6 @@ __global__ void __launch_bounds__(256) k_wx_scan_q1(const uint64_t* __restrict__
 // Hillis-Steele steps give; the three powers share one run of squarings
 // (Straus, a 4-bit sliding window per exponent): ~630 products against ~930.
 PA_DEV int ebit(const uint64_t* e, int b) { return (int)((e[b >> 6] >> (b & 63)) & 1); }
-PA_DEV dq::Q<1> pick8(const dq::Q<1> (&t)[8], int k) {
-    switch (k) {
-        case 0: return t[0];
-        case 1: return t[1];
-        case 2: return t[2];
-        case 3: return t[3];
-        case 4: return t[4];
-        case 5: return t[5];
-        case 6: return t[6];
-        default: return t[7];
-    }
-}
-PA_DEV void odd_powers(dq::Q<1> (&t)[8], const dq::Q<1>& x, const dq::Lc& l) {
-    t[0] = x;
-    const dq::Q<1> x2 = dq::sqr(x, l);
-#pragma unroll
-    for (int k = 1; k < 8; k++) t[k] = dq::mul(t[k - 1], x2, l);
-}
 // a 4-bit window of e opens at bit b (e's bit b set): its low end and value
 PA_DEV void open_window(const uint64_t* e, int b, int& lo, int& v) {
     int L = b - 3 < 0 ? 0 : b - 3;
@@ -506,78 +422,10 @@ PA_DEV void open_window(const uint64_t* e, int b, int& lo, int& v) {
     lo = L;
     v = val;
 }
-PA_DEV dq::Q<1> pow_multi3(const dq::Q<1>& x0, const dq::Q<1>& x1, const dq::Q<1>& x2, const uint64_t* e0,
-                           const uint64_t* e1, const uint64_t* e2, const dq::Lc& l) {
-    dq::Q<1> t0[8], t1[8], t2[8];
-    odd_powers(t0, x0, l);
-    odd_powers(t1, x1, l);
-    odd_powers(t2, x2, l);
-    int top = top_bit(e0);
-    top = top_bit(e1) > top ? top_bit(e1) : top;
-    top = top_bit(e2) > top ? top_bit(e2) : top;
-    int lo0 = -1, lo1 = -1, lo2 = -1, v0 = 0, v1 = 0, v2 = 0;
-    bool started = false;
-    dq::Q<1> acc = x0;
-    auto close = [&](const dq::Q<1> (&t)[8], int v) {
-        const dq::Q<1> f = pick8(t, v >> 1);
-        acc = started ? dq::mul(acc, f, l) : f;
-        started = true;
-    };
-#pragma unroll 1
-    for (int b = top; b >= 0; b--) {
-        if (lo0 < 0 && ebit(e0, b)) open_window(e0, b, lo0, v0);
-        if (lo1 < 0 && ebit(e1, b)) open_window(e1, b, lo1, v1);
-        if (lo2 < 0 && ebit(e2, b)) open_window(e2, b, lo2, v2);
-        if (started) acc = dq::sqr(acc, l);
-        if (lo0 == b) {
-            close(t0, v0);
-            lo0 = -1;
-        }
-        if (lo1 == b) {
-            close(t1, v1);
-            lo1 = -1;
-        }
-        if (lo2 == b) {
-            close(t2, v2);
-            lo2 = -1;
-        }
-    }
-    return acc;
-}
-
-__global__ void __launch_bounds__(256) k_wx_scan4_q1(const uint64_t* __restrict__ cin, uint64_t* __restrict__ cout,
-                                                     size_t N, size_t a, int s, const uint64_t* __restrict__ meta) {
-    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-    if (i >= N || meta[5 * 6]) return;   // whole quads leave together
-    const int lane = threadIdx.x & 63;
-    Fq v;
-    load(v, cin + 6 * i);
-    if (i >= a) {
-        const dq::Lc l = dq::lctx(lane, 1);
-        const dq::Q<1> one = dq::qconst(FL_ONE, l);
-        Fq p;
-        load(p, cin + 6 * (i - a));
-        const dq::Q<1> x0 = dq::from_abi(p, l);
-        dq::Q<1> x1 = one, x2 = one;
-        if (i >= 2 * a) {
-            load(p, cin + 6 * (i - 2 * a));
-            x1 = dq::from_abi(p, l);
-        }
-        if (i >= 3 * a) {
-            load(p, cin + 6 * (i - 3 * a));
-            x2 = dq::from_abi(p, l);
-        }
-        const dq::Q<1> t = pow_multi3(x0, x1, x2, PA_WX_E1[s], PA_WX_E1[s + 1], PA_WX_E1T[s], l);
-        v = dq::to_abi(dq::mul(dq::from_abi(v, l), t, l));
-    }
-    if ((lane & 3) == 0) store(cout + 6 * i, v);
-}
-
 // The radix-4 step one element per LANE on the lazy core's one-lane leaves:
 // 512 waves for 2^15 entries leave half the SIMDs idle and a lone wave's
 // product is ~1.1 us, but a quad product costs 2.5x the issue slots and the
 // quad form of these steps is issue-bound at two waves per SIMD
-// (PA_WX_SCAN4=quad selects it for A/B)
 PA_DEV F<1> pick8(const F<1> (&t)[8], int k) {
     switch (k) {
         case 0: return t[0];
@@ -650,7 +498,7 @@ __global__ void __launch_bounds__(64) k_wx_scan4_fl1(const uint64_t* __restrict_
 }
 
 // G2: one element per lane on the lazy core's Fq2 (tower_fl.h), z^(e0 + e1 q)
-// = z^e0 conj(z)^e1 over one run of squarings, as pow3 above
+// = z^e0 conj(z)^e1 (q = 3 mod 4: z^q = conj(z)) over one run of squarings
 __global__ void __launch_bounds__(64) k_wx_scan_fl2(const uint64_t* __restrict__ cin, uint64_t* __restrict__ cout,
                                                     size_t N, size_t off, int s, const uint64_t* __restrict__ meta) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -721,22 +569,6 @@ __global__ void __launch_bounds__(64) k_wx_serial(const uint64_t* __restrict__ b
         jac_add(b, d);
     }
 }
-
-// ---------------- fixed base: the multiply ----------------
-template <int G>
-__global__ void __launch_bounds__(64) k_wx_fixed_base_mul(const uint64_t* __restrict__ table,
-                                                          const uint64_t* __restrict__ scalars, size_t n, int window,
-                                                          int32_t* __restrict__ digits, uint64_t* __restrict__ out) {
-    using F = typename Wx<G>::F;
-    constexpr int JW = 3 * Wx<G>::W;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int len = wnaf_digits(scalars + 4 * i, window, digits + i, n);
-    Jac<F> r;
-    wnaf_exp<G>(r, table, 1, digits + i, n, len);
-    store_jac(out + (size_t)JW * i, r);
-}
-
 
 // ---------------- fixed base: the multiply on the lazy core ----------------
 template <int G>
@@ -853,33 +685,9 @@ __global__ void __launch_bounds__(64) k_wx_digit_keys(const uint64_t* __restrict
     idx[i] = (uint32_t)i;
 }
 
-// PA_WX_SORT=0: the scalars in their own order (A/B)
-bool wx_sort() {
-    static const bool v = !(getenv("PA_WX_SORT") && atoi(getenv("PA_WX_SORT")) == 0);
-    return v;
-}
-
-// PA_WX_MUL=word12: the round-5 multiply on the 12-word core (A/B); its
-// dense digit column needs the larger workspace (wx_layout)
-bool wx_mul_word12() {
-    static const bool v = getenv("PA_WX_MUL") && strcmp(getenv("PA_WX_MUL"), "word12") == 0;
-    return v;
-}
-
-bool wx_scan4_quad() {
-    static const bool v = getenv("PA_WX_SCAN4") && strcmp(getenv("PA_WX_SCAN4"), "quad") == 0;
-    return v;
-}
-// PA_WX_RADIX4=0: radix-2 steps only (A/B)
-bool wx_radix4() {
-    static const bool v = !(getenv("PA_WX_RADIX4") && atoi(getenv("PA_WX_RADIX4")) == 0);
-    return v;
-}
-
 template <int G>
 hipError_t wx_fixed_base(const uint64_t* base, const uint64_t* scalars, uint64_t* out, size_t n, int window,
                          void* workspace, hipStream_t stream) {
-    constexpr int W = Wx<G>::W;
     const size_t N = (size_t)1 << (window - 1);
     WxLayout L = wx_layout(G, n, window);
     char* ws = static_cast<char*>(workspace);
@@ -891,67 +699,45 @@ hipError_t wx_fixed_base(const uint64_t* base, const uint64_t* scalars, uint64_t
     int32_t* digits = reinterpret_cast<int32_t*>(ws + L.digits);
     const unsigned gb = blocks_for(N, 64);
     hipLaunchKernelGGL(k_wx_prep<G>, dim3(1), dim3(64), 0, stream, base, meta);
-    if (wx_mul_word12())
-        hipLaunchKernelGGL(k_wx_affine<G>, dim3(gb), dim3(64), 0, stream, base, N, aff, meta);
-    else
-        hipLaunchKernelGGL(k_wx_affine_fl<G>, dim3(gb), dim3(64), 0, stream, base, N, aff, meta);
+    hipLaunchKernelGGL(k_wx_affine_fl<G>, dim3(gb), dim3(64), 0, stream, base, N, aff, meta);
     hipLaunchKernelGGL(k_wx_coef<G>, dim3(gb), dim3(64), 0, stream, base, aff, N, c0, meta);
     int s = 0;
     for (size_t off = 1; off < N; off <<= 1, s++) {
-        if constexpr (G == 1) {
+        if constexpr (G == 2) {
+            hipLaunchKernelGGL(k_wx_scan_fl2, dim3(gb), dim3(64), 0, stream, c0, c1, N, off, s, meta);
+        } else if (s >= 8 && 2 * off < N) {
             // radix 4 where both steps' exponents are full size (3^(2^s) > q)
-            if (!wx_mul_word12() && wx_radix4() && s >= 8 && 2 * off < N) {
-                if (wx_scan4_quad())
-                    hipLaunchKernelGGL(k_wx_scan4_q1, dim3(blocks_for(4 * N, 256)), dim3(256), 0, stream, c0, c1, N,
-                                       off, s, meta);
-                else
-                    hipLaunchKernelGGL(k_wx_scan4_fl1, dim3(gb), dim3(64), 0, stream, c0, c1, N, off, s, meta);
-                uint64_t* t = c0;
-                c0 = c1;
-                c1 = t;
-                off <<= 1;
-                s++;
-                continue;
-            }
-        }
-        if (wx_mul_word12())
-            hipLaunchKernelGGL(k_wx_scan<G>, dim3(gb), dim3(64), 0, stream, c0, c1, N, off, s, meta);
-        else if constexpr (G == 1)
+            hipLaunchKernelGGL(k_wx_scan4_fl1, dim3(gb), dim3(64), 0, stream, c0, c1, N, off, s, meta);
+            off <<= 1;
+            s++;
+        } else {
             hipLaunchKernelGGL(k_wx_scan_q1, dim3(blocks_for(4 * N, 256)), dim3(256), 0, stream, c0, c1, N, off, s,
                                meta);
-        else
-            hipLaunchKernelGGL(k_wx_scan_fl2, dim3(gb), dim3(64), 0, stream, c0, c1, N, off, s, meta);
-        uint64_t* t = c0;
-        c0 = c1;
-        c1 = t;
+        }
+        std::swap(c0, c1);
     }
     hipLaunchKernelGGL(k_wx_finish<G>, dim3(gb), dim3(64), 0, stream, base, aff, c0, N, table, meta);
     hipLaunchKernelGGL(k_wx_serial<G>, dim3(1), dim3(64), 0, stream, base, N, table, meta);
     if (n == 0) return hipGetLastError();
-    if (wx_mul_word12()) {
-        hipLaunchKernelGGL(k_wx_fixed_base_mul<G>, dim3(blocks_for(n, 64)), dim3(64), 0, stream, table, scalars, n,
-                           window, digits, out);
-    } else {
-        uint32_t* tfl = reinterpret_cast<uint32_t*>(ws + L.tfl);
-        hipLaunchKernelGGL(k_wx_table_fl<G>, dim3(gb), dim3(64), 0, stream, table, N, tfl);
-        const uint32_t* perm = nullptr;
-        int32_t* cnts = nullptr;
-        if (wx_sort() && n <= 0x7fffffff) {
-            uint64_t* keys = reinterpret_cast<uint64_t*>(ws + L.keys);
-            uint32_t* idx = reinterpret_cast<uint32_t*>(ws + L.perm);
-            cnts = reinterpret_cast<int32_t*>(ws + L.cnts);
-            hipLaunchKernelGGL(k_wx_digit_keys, dim3(blocks_for(n, 64)), dim3(64), 0, stream, scalars, n, window,
-                               digits, cnts, keys, idx);
-            size_t tmp_bytes = L.sort_tmp_bytes;
-            hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + L.sort_tmp, tmp_bytes, keys, keys + n, idx,
-                                                              idx + n, (int)n, 0, 64, stream);
-            if (e != hipSuccess) return e;
-            perm = idx + n;
-        }
-        hipLaunchKernelGGL(k_wx_fixed_base_mul_fl<G>, dim3(blocks_for(n, 64)), dim3(64), 0, stream, tfl, scalars, n,
-                           window, digits, meta, perm, cnts, out);
+    uint32_t* tfl = reinterpret_cast<uint32_t*>(ws + L.tfl);
+    hipLaunchKernelGGL(k_wx_table_fl<G>, dim3(gb), dim3(64), 0, stream, table, N, tfl);
+    // the sort's item count is an int: above it the scalars run in their own order
+    const uint32_t* perm = nullptr;
+    int32_t* cnts = nullptr;
+    if (n <= 0x7fffffff) {
+        uint64_t* keys = reinterpret_cast<uint64_t*>(ws + L.keys);
+        uint32_t* idx = reinterpret_cast<uint32_t*>(ws + L.perm);
+        cnts = reinterpret_cast<int32_t*>(ws + L.cnts);
+        hipLaunchKernelGGL(k_wx_digit_keys, dim3(blocks_for(n, 64)), dim3(64), 0, stream, scalars, n, window, digits,
+                           cnts, keys, idx);
+        size_t tmp_bytes = L.sort_tmp_bytes;
+        hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + L.sort_tmp, tmp_bytes, keys, keys + n, idx, idx + n,
+                                                          (int)n, 0, 64, stream);
+        if (e != hipSuccess) return e;
+        perm = idx + n;
     }
-    (void)W;
+    hipLaunchKernelGGL(k_wx_fixed_base_mul_fl<G>, dim3(blocks_for(n, 64)), dim3(64), 0, stream, tfl, scalars, n, window,
+                       digits, meta, perm, cnts, out);
     return hipGetLastError();
 }
 
@@ -975,7 +761,7 @@ hipError_t wx_fixed_scalar(const uint64_t* bases, size_t n, const uint64_t* scal
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // workspace of the fixed-base path: meta, table, affine multiples, two scan
-// buffers, the digit columns of the n scalars
+// buffers, the packed nonzero-digit columns of the n scalars, the lazy table
 WxLayout wx_layout(int group, size_t n, int window) {
     const size_t W = group == 1 ? 6 : 12, N = (size_t)1 << (window - 1);
     WxLayout L;
@@ -991,9 +777,9 @@ WxLayout wx_layout(int group, size_t n, int window) {
     L.c1 = at;
     at = align256(at + 8 * W * N);
     L.digits = at;
-    at = align256(at + 4 * (size_t)(wx_mul_word12() ? kWxMaxDigits : wx_max_nonzero(window)) * n);
+    at = align256(at + 4 * (size_t)wx_max_nonzero(window) * n);
     L.tfl = at;
-    at = align256(at + (wx_mul_word12() ? 0 : 4 * (size_t)(group == 1 ? WxL<1>::EW : WxL<2>::EW) * N));
+    at = align256(at + 4 * (size_t)(group == 1 ? WxL<1>::EW : WxL<2>::EW) * N);
     // the scalar order of the multiply: keys and indices in and out of the sort
     L.keys = at;
     at = align256(at + 2 * 8 * n);

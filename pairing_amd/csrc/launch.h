@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "env.h"
+
 namespace pa {
 
 enum FieldOp : int {
@@ -48,15 +50,8 @@ struct StreamCfg {
     int prefetch;
 };
 inline StreamCfg stream_cfg() {
-    static const StreamCfg c = [] {
-        StreamCfg r{4096, 1};
-        if (const char* e = getenv("PA_STREAM_BLOCKS")) {
-            const long v = strtol(e, nullptr, 10);
-            if (v > 0) r.max_blocks = (size_t)v;
-        }
-        if (const char* e = getenv("PA_STREAM_PREFETCH")) r.prefetch = atoi(e) != 0;
-        return r;
-    }();
+    static const StreamCfg c{(size_t)env_within("PA_STREAM_BLOCKS", 4096, 1, LLONG_MAX),
+                             env_flag("PA_STREAM_PREFETCH", true)};
     return c;
 }
 
@@ -67,8 +62,6 @@ hipError_t launch_fq_mul_batch(const uint64_t* a, const uint64_t* b, uint64_t* o
                                hipStream_t stream);
 
 hipError_t launch_g2_prepare(const uint64_t* q_aff, uint64_t* prepared, size_t n, hipStream_t stream);
-hipError_t launch_miller_loop_prepared(const uint64_t* p_aff, const uint64_t* prepared, uint64_t* out,
-                                       size_t n, hipStream_t stream);
 // one G2Prepared (`prepared`, one record) for every G1 point of the batch:
 // the line table (kernels_pairing.hip) and the generated Miller loop over it
 constexpr int kSharedLineWords = 6 * 14;

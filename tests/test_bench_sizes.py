@@ -2,8 +2,9 @@
 
 bench.py measures the `_device` entry points (HBM-resident tensors through
 pairing_amd.device): config 2 is `pa_fq_mul_batch_device` at 2^20 elements
-(k_fq_mul_batch: grid-stride loop with register prefetch and a 4096-block
-grid cap), the Fr leg `pa_fr_mul_batch_device` at 2^20, config 4
+(k_fq_mul_batch_fl: one element per lane on the lazy 28-bit core), the Fr leg
+`pa_fr_mul_batch_device` at 2^20 (k_fr_mul_batch: grid-stride loop with
+register prefetch and a 4096-block grid cap), config 4
 `pa_pairing_batch_device` at 2^16 pairs on bench.make_pairs' inputs.  Each is
 compared here bit for bit with the oracle (fq.rs:909-960, fr.rs:438-465,
 mod.rs:40-160), at the benched size and at a ragged size that leaves a

@@ -4,7 +4,7 @@ pa_g2_multiexp_device over n random terms, HIP events on the launch stream,
 median of 5; the result checked against the G1-free identity
 sum s_i (a_i G2) = (sum s_i a_i) G2 through the oracle.
 
-  python tools/msm_g2_probe.py [n ...]      (PA_MSM_G2_LAZY=0: the 12-word kernels)"""
+  python tools/msm_g2_probe.py [n ...]"""
 import os
 import sys
 
@@ -45,5 +45,4 @@ for n in [int(x) for x in sys.argv[1:]] or [1 << 16]:
     tot = sum(x * y for x, y in zip(a, s)) % R
     ok = bool((o.g2_into_affine(out.cpu().numpy().view(np.uint64)) == o.g2_mul_generator(scal([tot]))).all())
     ms = sorted(ts)[len(ts) // 2]
-    print("G2 MSM n=%d  lazy=%s  %.3f ms  %.2f M terms/s  ok=%s" % (n, os.environ.get("PA_MSM_G2_LAZY", "1"), ms,
-                                                                   n / ms / 1e3, ok), flush=True)
+    print("G2 MSM n=%d  %.3f ms  %.2f M terms/s  ok=%s" % (n, ms, n / ms / 1e3, ok), flush=True)

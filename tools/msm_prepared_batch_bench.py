@@ -33,7 +33,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KNOBS = ("PA_MSM_BATCH_C", "PA_MSM_BATCH_PARTS", "PA_MSM_GLV_C", "PA_MSM_GLV_LONGSPAN", "PA_MSM_PARTS",
-         "PA_MSM_CHUNK", "PA_MSM_WLO", "PA_MSM_CMAX", "PA_MSM_SEG", "PA_MSM_ACC", "PA_LIB_PATH")
+         "PA_MSM_CHUNK", "PA_MSM_WLO", "PA_MSM_CMAX", "PA_MSM_SEG", "PA_LIB_PATH")
 SHAPES = "12x1,12x256,16x1,16x4,16x16,16x64,18x1,18x8,20x1,20x4"
 
 

@@ -15,7 +15,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = {"k_decode<2, true>": "g2_decode_compressed", "k_decode<1, true>": "g1_decode_compressed",
-        "k_msm_chunk_acc_fl": "g1_msm_chunk_acc", "k_msm_horner_fl": "g1_msm_horner"}
+        "k_msm_chunk_acc_fl": "g1_msm_chunk_acc", "k_msm_horner_q<1>": "g1_msm_horner"}
 
 
 def main():
