@@ -436,6 +436,38 @@ int pa_g1_multiexp_prepared_batch_device(const pa_g1_msm_bases *bases, const voi
 int pa_g1_multiexp_prepared_batch(const pa_g1_msm_bases *bases, const void *host_scalars, size_t m, size_t k,
                                   unsigned flags, pa_g1 *out);
 
+/* ---- G2 multiexp over prepared bases ----
+ * The G1 block above, one for one, over pa_g2_affine bases and pa_g2 results:
+ * the same object rules, error codes, flags, zero sizes (k = 0 writes
+ * nothing, m = 0 writes k zero points) and 32-bit item limit, and one vector
+ * with PA_MSM_SCALARS_REPR runs the job of pa_g2_multiexp_prepared_device.
+ * The flag is the G2 membership test of pa_g2_subgroup_check_batch.  With it
+ * set, the scalar splits s = q x^2 + rem as for G1 and the second half runs
+ * over x^2 Q_i, which costs one Fq product per coordinate word: with beta the
+ * cube root of unity of the G1 path and Q = (x, y) in G2,
+ *     x^2 Q = (beta^2 x, -y)        (x = 0xd201000000010000; beta^2 scales
+ *                                    both Fq components of the Fq2 coordinate)
+ * and not (beta x, -y), which is the G1 relation and fails on G2.  With the
+ * flag clear the 257-bit pipeline of pa_g2_multiexp runs over the prepared
+ * rows; nothing is converted per call either way.  Results are equal as
+ * points to the reference's sum for every 256-bit FrRepr. */
+typedef struct pa_g2_msm_bases pa_g2_msm_bases;
+int pa_g2_msm_bases_prepare(const pa_g2_affine *host_bases, size_t n, pa_g2_msm_bases **out);
+int pa_g2_msm_bases_prepare_device(const pa_g2_affine *dev_bases, size_t n, void *stream, pa_g2_msm_bases **out);
+size_t pa_g2_msm_bases_len(const pa_g2_msm_bases *bases);
+int pa_g2_msm_bases_in_subgroup(const pa_g2_msm_bases *bases);   /* 1 or 0 */
+int pa_g2_msm_bases_free(pa_g2_msm_bases *bases);
+size_t pa_g2_multiexp_prepared_workspace_bytes(const pa_g2_msm_bases *bases, size_t m);
+int pa_g2_multiexp_prepared_device(const pa_g2_msm_bases *bases, const pa_fr_repr *dev_scalars, size_t m,
+                                   pa_g2 *dev_out, void *workspace, size_t workspace_bytes, void *stream);
+int pa_g2_multiexp_prepared(const pa_g2_msm_bases *bases, const pa_fr_repr *host_scalars, size_t m, pa_g2 *out);
+size_t pa_g2_multiexp_prepared_batch_workspace_bytes(const pa_g2_msm_bases *bases, size_t m, size_t k);
+int pa_g2_multiexp_prepared_batch_device(const pa_g2_msm_bases *bases, const void *dev_scalars, size_t m, size_t k,
+                                         unsigned flags, pa_g2 *dev_out, void *workspace, size_t workspace_bytes,
+                                         void *stream);
+int pa_g2_multiexp_prepared_batch(const pa_g2_msm_bases *bases, const void *host_scalars, size_t m, size_t k,
+                                  unsigned flags, pa_g2 *out);
+
 /* ---- scalar field Fr (src/bls12_381/fr.rs; SURVEY.md §8 f, rank 4) ----
  * pa_fr = 4 x u64 LE limbs, Montgomery form with R = 2^256, < r: the
  * reference's `Fr` in memory.  Every result is canonical, so it equals the

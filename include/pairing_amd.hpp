@@ -578,59 +578,94 @@ PA_AFFINE_DEFS(G1Affine, G1, 1)
 PA_AFFINE_DEFS(G2Affine, G2, 2)
 #undef PA_AFFINE_DEFS
 
-// G1 multiexp bases prepared once (pa_g1_msm_bases): the membership check and
-// the conversion pa_g1_multiexp repeats per call, kept on the current device.
-// Move-only; the destructor frees the device memory.
-class G1MsmBases {
+// Multiexp bases prepared once (pa_g1_msm_bases, pa_g2_msm_bases): the
+// membership check and the conversion pa_g{1,2}_multiexp repeats per call, kept
+// on the current device.  Move-only; the destructor frees the device memory.
+// G1MsmBases and G2MsmBases below are this class over the group's C entries.
+template <class Abi>
+class MsmBases {
 public:
-    explicit G1MsmBases(const std::vector<G1Affine>& bases) {
-        check(pa_g1_msm_bases_prepare(bases.empty() ? nullptr : &bases[0].v, bases.size(), &h_), "G1MsmBases");
+    using Affine = typename Abi::Affine;
+    using Point = typename Abi::Point;
+    explicit MsmBases(const std::vector<Affine>& bases) {
+        check(Abi::prepare(bases.empty() ? nullptr : &bases[0].v, bases.size(), &h_), Abi::name);
     }
-    G1MsmBases(const G1MsmBases&) = delete;
-    G1MsmBases& operator=(const G1MsmBases&) = delete;
-    G1MsmBases(G1MsmBases&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
-    G1MsmBases& operator=(G1MsmBases&& o) noexcept {
+    MsmBases(const MsmBases&) = delete;
+    MsmBases& operator=(const MsmBases&) = delete;
+    MsmBases(MsmBases&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    MsmBases& operator=(MsmBases&& o) noexcept {
         if (this != &o) {
-            (void)pa_g1_msm_bases_free(h_);
+            (void)Abi::free(h_);
             h_ = o.h_;
             o.h_ = nullptr;
         }
         return *this;
     }
-    ~G1MsmBases() { (void)pa_g1_msm_bases_free(h_); }
+    ~MsmBases() { (void)Abi::free(h_); }
 
-    size_t size() const { return pa_g1_msm_bases_len(h_); }
-    bool in_subgroup() const { return pa_g1_msm_bases_in_subgroup(h_) != 0; }
-    const pa_g1_msm_bases* get() const { return h_; }
+    size_t size() const { return Abi::len(h_); }
+    bool in_subgroup() const { return Abi::in_subgroup(h_) != 0; }
+    const typename Abi::Handle* get() const { return h_; }
     // sum_i s_i * bases_i over the first s.size() <= size() bases: the same
-    // point as G1::multiexp over them
-    G1 multiexp(const std::vector<FrRepr>& s) const {
-        G1 r;
-        check(pa_g1_multiexp_prepared(h_, s.empty() ? nullptr : &s[0].v, s.size(), &r.v), "G1MsmBases::multiexp");
+    // point as the group's multiexp over them
+    Point multiexp(const std::vector<FrRepr>& s) const {
+        Point r;
+        check(Abi::multiexp(h_, s.empty() ? nullptr : &s[0].v, s.size(), &r.v), Abi::name_multiexp);
         return r;
     }
     // k vectors of s.size() / k scalars end to end, one pipeline: result j is
     // sum_i s[j m + i] * bases_i, the same point as multiexp over that vector
-    std::vector<G1> multiexp_batch(const std::vector<FrRepr>& s, size_t k) const {
+    std::vector<Point> multiexp_batch(const std::vector<FrRepr>& s, size_t k) const {
         static_assert(sizeof(FrRepr) == sizeof(pa_fr_repr), "FrRepr rows are pa_fr_repr rows");
         return batch(s.empty() ? nullptr : &s[0].v, s.size(), k, PA_MSM_SCALARS_REPR);
     }
     // ... over Montgomery rows below r (what FrNttDomain's transforms return)
-    std::vector<G1> multiexp_batch(const std::vector<pa_fr>& s, size_t k) const {
+    std::vector<Point> multiexp_batch(const std::vector<pa_fr>& s, size_t k) const {
         return batch(s.data(), s.size(), k, PA_MSM_SCALARS_MONTGOMERY);
     }
 
 private:
-    std::vector<G1> batch(const void* s, size_t rows, size_t k, unsigned flags) const {
+    std::vector<Point> batch(const void* s, size_t rows, size_t k, unsigned flags) const {
         if (k ? rows % k != 0 : rows != 0)
-            throw std::invalid_argument("G1MsmBases::multiexp_batch: rows are not k vectors of equal length");
-        static_assert(sizeof(G1) == sizeof(pa_g1), "G1 rows are pa_g1 rows");
-        std::vector<G1> r(k);
-        if (k) check(pa_g1_multiexp_prepared_batch(h_, s, rows / k, k, flags, &r[0].v), "G1MsmBases::multiexp_batch");
+            throw std::invalid_argument(std::string(Abi::name_batch) + ": rows are not k vectors of equal length");
+        static_assert(sizeof(Point) == sizeof(decltype(Point::v)), "point rows are ABI rows");
+        std::vector<Point> r(k);
+        if (k) check(Abi::multiexp_batch(h_, s, rows / k, k, flags, &r[0].v), Abi::name_batch);
         return r;
     }
-    pa_g1_msm_bases* h_ = nullptr;
+    typename Abi::Handle* h_ = nullptr;
 };
+struct G1MsmAbi {
+    using Affine = G1Affine;
+    using Point = G1;
+    using Handle = pa_g1_msm_bases;
+    static constexpr auto prepare = &pa_g1_msm_bases_prepare;
+    static constexpr auto free = &pa_g1_msm_bases_free;
+    static constexpr auto len = &pa_g1_msm_bases_len;
+    static constexpr auto in_subgroup = &pa_g1_msm_bases_in_subgroup;
+    static constexpr auto multiexp = &pa_g1_multiexp_prepared;
+    static constexpr auto multiexp_batch = &pa_g1_multiexp_prepared_batch;
+    static constexpr const char* name = "G1MsmBases";
+    static constexpr const char* name_multiexp = "G1MsmBases::multiexp";
+    static constexpr const char* name_batch = "G1MsmBases::multiexp_batch";
+};
+struct G2MsmAbi {
+    using Affine = G2Affine;
+    using Point = G2;
+    using Handle = pa_g2_msm_bases;
+    static constexpr auto prepare = &pa_g2_msm_bases_prepare;
+    static constexpr auto free = &pa_g2_msm_bases_free;
+    static constexpr auto len = &pa_g2_msm_bases_len;
+    static constexpr auto in_subgroup = &pa_g2_msm_bases_in_subgroup;
+    static constexpr auto multiexp = &pa_g2_multiexp_prepared;
+    static constexpr auto multiexp_batch = &pa_g2_multiexp_prepared_batch;
+    static constexpr const char* name = "G2MsmBases";
+    static constexpr const char* name_multiexp = "G2MsmBases::multiexp";
+    static constexpr const char* name_batch = "G2MsmBases::multiexp_batch";
+};
+using G1MsmBases = MsmBases<G1MsmAbi>;
+// x^2 Q = (beta^2 x, -y) on G2 is what its second half of every scalar runs over (pairing_amd.h)
+using G2MsmBases = MsmBases<G2MsmAbi>;
 
 // A radix-2 evaluation domain of 2^log_n points over Fr (pa_fr_ntt_domain): the
 // fft / ifft / coset_fft / icoset_fft of a prover, over `batch` polynomials laid

@@ -16,8 +16,8 @@ Device-resident entry points for torch tensors live in `pairing_amd.device`.
 """
 import numpy as np
 
-from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, NTT_MAX_LOG_N, FrNttDomain, G1MsmBases,
-                      PairingError, _lib, as_rows, batch_shape, call, csr_offsets, device_count, msm_scalars, ntt_mode, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
+from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, NTT_MAX_LOG_N, FrNttDomain, G1MsmBases, G2MsmBases,
+                      PairingError, _lib, as_rows, batch_shape, call, csr_offsets, device_count, msm_bases, msm_scalars, ntt_mode, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
 
 __all__ = [
     "PairingError", "version", "device_count", "set_device", "set_pairing_kernel", "set_decode_kernel",
@@ -34,6 +34,7 @@ __all__ = [
     "fr_from_repr", "fr_into_repr", "fr_pow", "fr_legendre", "fr_sqrt",
     "g1_affine_mul", "g2_affine_mul", "g1_mul_assign", "g2_mul_assign", "g1_multiexp", "g2_multiexp",
     "G1MsmBases", "g1_msm_prepare", "g1_multiexp_prepared", "g1_multiexp_prepared_batch",
+    "G2MsmBases", "g2_msm_prepare", "g2_multiexp_prepared", "g2_multiexp_prepared_batch",
     "FrNttDomain", "fr_ntt_domain", "fr_ntt",
     "g1_eq", "g2_eq", "g1_double", "g2_double", "g1_add", "g2_add", "g1_add_mixed", "g2_add_mixed", "g1_negate", "g2_negate",
     "g1_sub", "g2_sub", "g1_into_affine", "g2_into_affine", "g1_into_projective", "g2_into_projective",
@@ -608,28 +609,51 @@ def g2_multiexp(bases, scalars):
     return _multiexp("pa_g2_multiexp", bases, scalars, W_G2A, W_G2)
 
 
+# the prepared entries of both groups: (handle class, affine width, Jacobian width)
+_MSM_GROUPS = {1: (G1MsmBases, W_G1A, W_G1), 2: (G2MsmBases, W_G2A, W_G2)}
+
+
+def _msm_prepare(group, bases):
+    import ctypes
+    cls, in_width, _ = _MSM_GROUPS[group]
+    b = as_rows(bases, in_width, "bases") if len(bases) else np.zeros((0, in_width), np.uint64)
+    h = ctypes.c_void_p(0)
+    call("pa_g%d_msm_bases_prepare" % group, ptr(b), b.shape[0], ctypes.byref(h))
+    return cls._adopt(h)
+
+
+def _multiexp_prepared(group, prepared, scalars):
+    cls, _, out_width = _MSM_GROUPS[group]
+    msm_bases(prepared, cls, "g%d_msm_prepare" % group)
+    s = as_rows(scalars, 4, "scalars") if len(scalars) else np.zeros((0, 4), np.uint64)
+    h = prepared.check_terms(s.shape[0])
+    out = np.zeros((1, out_width), np.uint64)
+    call("pa_g%d_multiexp_prepared" % group, h, ptr(s), s.shape[0], ptr(out))
+    return out
+
+
+def _multiexp_prepared_batch(group, prepared, scalars, count, montgomery):
+    cls, _, out_width = _MSM_GROUPS[group]
+    msm_bases(prepared, cls, "g%d_msm_prepare" % group)
+    flags = msm_scalars(montgomery)
+    s, k, m = batch_shape(scalars, count)
+    h = prepared.check_terms(m)
+    out = np.zeros((k, out_width), np.uint64)
+    call("pa_g%d_multiexp_prepared_batch" % group, h, ptr(s), m, k, flags, ptr(out))
+    return out
+
+
 def g1_msm_prepare(bases):
     """Prepare G1 affine bases ((n, 13) rows) for repeated multiexps: checked for G1
     membership and converted once, kept on the current device.  Returns a G1MsmBases
     (len, in_subgroup, close()); free it with close() or let it be collected."""
-    import ctypes
-    b = as_rows(bases, W_G1A, "bases") if len(bases) else np.zeros((0, W_G1A), np.uint64)
-    h = ctypes.c_void_p(0)
-    call("pa_g1_msm_bases_prepare", ptr(b), b.shape[0], ctypes.byref(h))
-    return G1MsmBases._adopt(h)
+    return _msm_prepare(1, bases)
 
 
 def g1_multiexp_prepared(prepared, scalars):
     """sum_i s_i * P_i over the first len(scalars) prepared bases: one Jacobian row, the
     same point as g1_multiexp over those bases (any 256-bit FrRepr)."""
-    if not isinstance(prepared, G1MsmBases):
-        raise ValueError("prepared must come from g1_msm_prepare")
-    prepared.handle()   # a closed object is rejected first
-    s = as_rows(scalars, 4, "scalars") if len(scalars) else np.zeros((0, 4), np.uint64)
-    h = prepared.check_terms(s.shape[0])
-    out = np.zeros((1, W_G1), np.uint64)
-    call("pa_g1_multiexp_prepared", h, ptr(s), s.shape[0], ptr(out))
-    return out
+    return _multiexp_prepared(1, prepared, scalars)
 
 
 def g1_multiexp_prepared_batch(prepared, scalars, count=None, montgomery=False):
@@ -638,15 +662,25 @@ def g1_multiexp_prepared_batch(prepared, scalars, count=None, montgomery=False):
     sum_i s[j][i] * P_i over the first m prepared bases, the same point as
     g1_multiexp_prepared(prepared, s[j]).  The rows are FrRepr (any 256-bit value),
     or with montgomery=True Montgomery Fr below r (what fr_ntt returns)."""
-    if not isinstance(prepared, G1MsmBases):
-        raise ValueError("prepared must come from g1_msm_prepare")
-    prepared.handle()   # a closed object is rejected first
-    flags = msm_scalars(montgomery)
-    s, k, m = batch_shape(scalars, count)
-    h = prepared.check_terms(m)
-    out = np.zeros((k, W_G1), np.uint64)
-    call("pa_g1_multiexp_prepared_batch", h, ptr(s), m, k, flags, ptr(out))
-    return out
+    return _multiexp_prepared_batch(1, prepared, scalars, count, montgomery)
+
+
+def g2_msm_prepare(bases):
+    """g1_msm_prepare for G2 affine bases ((n, 25) rows): returns a G2MsmBases.  A G1
+    object is not a G2 one: each group's functions take only their own (ValueError)."""
+    return _msm_prepare(2, bases)
+
+
+def g2_multiexp_prepared(prepared, scalars):
+    """sum_i s_i * Q_i over the first len(scalars) prepared G2 bases: one Jacobian row
+    (1, 36), the same point as g2_multiexp over those bases (any 256-bit FrRepr)."""
+    return _multiexp_prepared(2, prepared, scalars)
+
+
+def g2_multiexp_prepared_batch(prepared, scalars, count=None, montgomery=False):
+    """g1_multiexp_prepared_batch over prepared G2 bases: a (k, 36) result, row j the
+    same point as g2_multiexp_prepared(prepared, s[j])."""
+    return _multiexp_prepared_batch(2, prepared, scalars, count, montgomery)
 
 
 # ---- batched Fr NTT over radix-2 evaluation domains ----

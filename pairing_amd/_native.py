@@ -159,6 +159,17 @@ _SIGS = {
     "pa_g1_multiexp_prepared_batch_workspace_bytes": [_P, _N, _N],   # returns size_t (below)
     "pa_g1_multiexp_prepared_batch_device": [_P, _P, _N, _N, ctypes.c_uint, _P, _P, _N, _P],
     "pa_g1_multiexp_prepared_batch": [_P, _P, _N, _N, ctypes.c_uint, _P],
+    "pa_g2_msm_bases_prepare": [_P, _N, ctypes.POINTER(_P)],
+    "pa_g2_msm_bases_prepare_device": [_P, _N, _P, ctypes.POINTER(_P)],
+    "pa_g2_msm_bases_len": [_P],                      # returns size_t (below)
+    "pa_g2_msm_bases_in_subgroup": [_P],
+    "pa_g2_msm_bases_free": [_P],
+    "pa_g2_multiexp_prepared_workspace_bytes": [_P, _N],   # returns size_t (below)
+    "pa_g2_multiexp_prepared_device": [_P, _P, _N, _P, _P, _N, _P],
+    "pa_g2_multiexp_prepared": [_P, _P, _N, _P],
+    "pa_g2_multiexp_prepared_batch_workspace_bytes": [_P, _N, _N],   # returns size_t (below)
+    "pa_g2_multiexp_prepared_batch_device": [_P, _P, _N, _N, ctypes.c_uint, _P, _P, _N, _P],
+    "pa_g2_multiexp_prepared_batch": [_P, _P, _N, _N, ctypes.c_uint, _P],
     "pa_fr_ntt_domain_create": [ctypes.c_uint, ctypes.POINTER(_P)],
     "pa_fr_ntt_domain_free": [_P],                    # returns nothing (below)
     "pa_fr_ntt_domain_log_n": [_P],                   # returns unsigned (below)
@@ -219,9 +230,9 @@ _lib.pa_multiexp_workspace_bytes.argtypes = [ctypes.c_int, _N]
 _lib.pa_multiexp_workspace_bytes.restype = ctypes.c_size_t
 _lib.pa_wnaf_exact_workspace_bytes.argtypes = [ctypes.c_int, _N, ctypes.c_int, ctypes.c_int]
 _lib.pa_wnaf_exact_workspace_bytes.restype = ctypes.c_size_t
-_lib.pa_g1_msm_bases_len.restype = ctypes.c_size_t
-_lib.pa_g1_multiexp_prepared_workspace_bytes.restype = ctypes.c_size_t
-_lib.pa_g1_multiexp_prepared_batch_workspace_bytes.restype = ctypes.c_size_t
+for _g in (1, 2):
+    for _name in ("msm_bases_len", "multiexp_prepared_workspace_bytes", "multiexp_prepared_batch_workspace_bytes"):
+        getattr(_lib, "pa_g%d_%s" % (_g, _name)).restype = ctypes.c_size_t
 _lib.pa_multi_pairing_batch_workspace_bytes.restype = ctypes.c_size_t
 _lib.pa_fr_ntt_domain_free.restype = None
 for _name in ("pa_fr_ntt_domain_log_n", "pa_fr_ntt_domain_passes", "pa_fr_ntt_domain_tile_log", "pa_fr_ntt_max_log_n"):
@@ -305,12 +316,15 @@ def csr_offsets(offsets, n):
     return o
 
 
-class G1MsmBases:
-    """A pa_g1_msm_bases handle: G1 multiexp bases prepared once on one device
-    (include/pairing_amd.h).  `len` and `in_subgroup` are read at creation;
-    close() frees the device memory, is idempotent and also runs when the
-    object is collected.  Any use after close() raises ValueError before a
-    native call.  owns=False wraps a handle someone else frees."""
+class _MsmBases:
+    """A pa_g{1,2}_msm_bases handle: multiexp bases of one group prepared once on
+    one device (include/pairing_amd.h).  `len` and `in_subgroup` are read at
+    creation; close() frees the device memory, is idempotent and also runs when
+    the object is collected.  Any use after close() raises ValueError before a
+    native call.  owns=False wraps a handle someone else frees.  The two groups
+    are sibling subclasses: neither passes for the other."""
+
+    GROUP = 0   # 1 or 2: the pa_g{GROUP}_* entries this handle belongs to
 
     def __init__(self, handle, length, in_subgroup, owns=True):
         self._handle = handle
@@ -322,7 +336,8 @@ class G1MsmBases:
     def _adopt(cls, handle):
         """take ownership of a handle a prepare call just returned"""
         h = ctypes.c_void_p(handle.value)
-        return cls(h, _lib.pa_g1_msm_bases_len(h), _lib.pa_g1_msm_bases_in_subgroup(h))
+        return cls(h, getattr(_lib, "pa_g%d_msm_bases_len" % cls.GROUP)(h),
+                   getattr(_lib, "pa_g%d_msm_bases_in_subgroup" % cls.GROUP)(h))
 
     def __len__(self):
         return self.len
@@ -346,7 +361,7 @@ class G1MsmBases:
     def close(self):
         h, self._handle = self._handle, None
         if h is not None and self._owns:
-            call("pa_g1_msm_bases_free", h)
+            call("pa_g%d_msm_bases_free" % self.GROUP, h)
 
     def __enter__(self):
         return self
@@ -359,6 +374,25 @@ class G1MsmBases:
             self.close()
         except Exception:   # interpreter shutdown: the library may be gone
             pass
+
+
+class G1MsmBases(_MsmBases):
+    """prepared G1 bases (pa_g1_msm_bases)"""
+    GROUP = 1
+
+
+class G2MsmBases(_MsmBases):
+    """prepared G2 bases (pa_g2_msm_bases)"""
+    GROUP = 2
+
+
+def msm_bases(prepared, cls, maker):
+    """`prepared` if it is a live handle of class cls (G1MsmBases or G2MsmBases),
+    else a ValueError: another group's handle, a closed one, anything else"""
+    if not isinstance(prepared, cls):
+        raise ValueError("prepared must come from %s" % maker)
+    prepared.handle()   # a closed object is rejected first
+    return prepared
 
 
 MSM_SCALARS_REPR, MSM_SCALARS_MONTGOMERY = 0, 1   # PA_MSM_SCALARS_* of the header

@@ -1575,17 +1575,21 @@ int pa_g2_multiexp_device(const pa_g2_affine* bases, const pa_fr_repr* scalars, 
     return PA_OK;
 }
 
-// ---- G1 MSM over prepared bases (kernels_msm.hip) ----
+// ---- MSM over prepared bases, G1 and G2 (kernels_msm.hip) ----
 // The object owns the 2n lazy rows on one device and remembers whether every
-// base passed the G1 membership test: the host picks the GLV pipeline (flag 1)
-// or the 257-bit one over the same rows (flag 0) from it.
-struct pa_g1_msm_bases {
+// base passed the group's membership test: the host picks the GLV pipeline
+// (flag 1) or the 257-bit one over the same rows (flag 0) from it.  Both
+// groups' entries are the same code over MsmAbi<G>.
+struct MsmBasesObj {
     int dev = 0;
     size_t n = 0;
     int in_subgroup = 0;
     uint32_t* rows = nullptr;
 };
+struct pa_g1_msm_bases : MsmBasesObj {};
+struct pa_g2_msm_bases : MsmBasesObj {};
 
+extern "C++" {   // templates
 namespace {
 // the current device switched to `dev` for a scope (allocations belong to the current device)
 struct DeviceScope {
@@ -1601,9 +1605,36 @@ struct DeviceScope {
         if (switched) (void)hipSetDevice(prev);
     }
 };
-}  // namespace
 
-int pa_g1_msm_bases_prepare_device(const pa_g1_affine* bases, size_t n, void* stream, pa_g1_msm_bases** out) {
+// the group's records, launchers and the entry names its messages quote
+template <int G> struct MsmAbi;
+template <> struct MsmAbi<1> {
+    using Bases = pa_g1_msm_bases;
+    using Affine = pa_g1_affine;
+    using Point = pa_g1;
+    static constexpr auto prepare = pa::launch_msm_prepare_g1;
+    static constexpr auto single = pa::launch_msm_prepared_g1;
+    static constexpr auto batch = pa::launch_msm_prepared_g1_batch;
+    static constexpr const char* small_ws = "workspace smaller than pa_g1_multiexp_prepared_workspace_bytes";
+    static constexpr const char* small_batch_ws =
+        "workspace smaller than pa_g1_multiexp_prepared_batch_workspace_bytes";
+};
+template <> struct MsmAbi<2> {
+    using Bases = pa_g2_msm_bases;
+    using Affine = pa_g2_affine;
+    using Point = pa_g2;
+    static constexpr auto prepare = pa::launch_msm_prepare_g2;
+    static constexpr auto single = pa::launch_msm_prepared_g2;
+    static constexpr auto batch = pa::launch_msm_prepared_g2_batch;
+    static constexpr const char* small_ws = "workspace smaller than pa_g2_multiexp_prepared_workspace_bytes";
+    static constexpr const char* small_batch_ws =
+        "workspace smaller than pa_g2_multiexp_prepared_batch_workspace_bytes";
+};
+
+template <int G>
+int msm_bases_prepare_device(const typename MsmAbi<G>::Affine* bases, size_t n, void* stream,
+                             typename MsmAbi<G>::Bases** out) {
+    using Bases = typename MsmAbi<G>::Bases;
     if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
     *out = nullptr;
     if (n && !bases) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
@@ -1613,7 +1644,7 @@ int pa_g1_msm_bases_prepare_device(const pa_g1_affine* bases, size_t n, void* st
     PA_TRY(hipStreamGetDevice(s, &dev), "stream device");
     DeviceScope scope;
     PA_TRY(scope.enter(dev), "set device");
-    pa_g1_msm_bases* b = new pa_g1_msm_bases;
+    Bases* b = new Bases;
     b->dev = dev;
     b->n = n;
     b->in_subgroup = 1;
@@ -1625,11 +1656,11 @@ int pa_g1_msm_bases_prepare_device(const pa_g1_affine* bases, size_t n, void* st
     const size_t bad_off = (n + 255) & ~(size_t)255;
     uint8_t* scratch = nullptr;
     uint32_t bad = 0;
-    hipError_t e = hipMalloc((void**)&b->rows, pa::msm_prepared_rows_bytes(n));
+    hipError_t e = hipMalloc((void**)&b->rows, pa::msm_prepared_rows_bytes(n, G));
     if (e == hipSuccess) e = hipMalloc((void**)&scratch, bad_off + sizeof(uint32_t));
     uint32_t* dbad = reinterpret_cast<uint32_t*>(scratch + bad_off);
-    if (e == hipSuccess) e = pa::launch_subgroup_check(1, (const uint64_t*)bases, n, scratch, s);
-    if (e == hipSuccess) e = pa::launch_msm_prepare_g1((const uint64_t*)bases, scratch, n, b->rows, dbad, s);
+    if (e == hipSuccess) e = pa::launch_subgroup_check(G, (const uint64_t*)bases, n, scratch, s);
+    if (e == hipSuccess) e = MsmAbi<G>::prepare((const uint64_t*)bases, scratch, n, b->rows, dbad, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, s);
     const hipError_t sync = hipStreamSynchronize(s);   // also before the scratch goes, whatever failed above
     if (e == hipSuccess) e = sync;
@@ -1643,110 +1674,148 @@ int pa_g1_msm_bases_prepare_device(const pa_g1_affine* bases, size_t n, void* st
     *out = b;
     return PA_OK;
 }
-int pa_g1_msm_bases_prepare(const pa_g1_affine* bases, size_t n, pa_g1_msm_bases** out) {
+template <int G>
+int msm_bases_prepare(const typename MsmAbi<G>::Affine* bases, size_t n, typename MsmAbi<G>::Bases** out) {
     if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
     *out = nullptr;
     if (n && !bases) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
     if (n >= pa::kMsmPreparedMax) return fail(PA_ERR_INVALID_ARGUMENT, "prepared multiexp bases support n < 2^30");
     DevBuf db;
     int rc;
-    if ((rc = upload(db, bases, sizeof(pa_g1_affine) * n))) return rc;
-    return pa_g1_msm_bases_prepare_device(db.as<pa_g1_affine>(), n, call_stream(), out);
+    if ((rc = upload(db, bases, sizeof(typename MsmAbi<G>::Affine) * n))) return rc;
+    return msm_bases_prepare_device<G>(db.as<typename MsmAbi<G>::Affine>(), n, call_stream(), out);
 }
-size_t pa_g1_msm_bases_len(const pa_g1_msm_bases* b) { return b ? b->n : 0; }
-int pa_g1_msm_bases_in_subgroup(const pa_g1_msm_bases* b) { return b ? b->in_subgroup : 0; }
-int pa_g1_msm_bases_free(pa_g1_msm_bases* b) {
+template <class Bases>
+int msm_bases_free(Bases* b) {
     if (!b) return PA_OK;
     const hipError_t e = b->rows ? hipFree(b->rows) : hipSuccess;
     delete b;
     if (e != hipSuccess) return fail(hip_code(e), "free multiexp bases", e);
     return PA_OK;
 }
-size_t pa_g1_multiexp_prepared_workspace_bytes(const pa_g1_msm_bases* b, size_t m) {
-    return b && m <= b->n ? pa::msm_prepared_workspace_bytes(m, b->in_subgroup != 0) : 0;
-}
-int pa_g1_multiexp_prepared_device(const pa_g1_msm_bases* b, const pa_fr_repr* scalars, size_t m, pa_g1* out,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
+template <int G>
+int msm_prepared_device(const typename MsmAbi<G>::Bases* b, const pa_fr_repr* scalars, size_t m,
+                        typename MsmAbi<G>::Point* out, void* workspace, size_t workspace_bytes, void* stream) {
     if (!b || !out || (m && (!scalars || !workspace))) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
     if (m > b->n) return fail(PA_ERR_INVALID_ARGUMENT, "more scalars than prepared bases");
-    if (m && workspace_bytes < pa::msm_prepared_workspace_bytes(m, b->in_subgroup != 0))
-        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_g1_multiexp_prepared_workspace_bytes");
+    if (m && workspace_bytes < pa::msm_prepared_workspace_bytes(m, b->in_subgroup != 0, G))
+        return fail(PA_ERR_INVALID_ARGUMENT, MsmAbi<G>::small_ws);
     int dev = 0;
     PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
     if (dev != b->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the prepared bases");
-    PA_TRY(pa::launch_msm_prepared_g1(b->rows, b->n, b->in_subgroup != 0, (const uint64_t*)scalars, m, (uint64_t*)out,
-                                      workspace, workspace_bytes, (hipStream_t)stream),
+    PA_TRY(MsmAbi<G>::single(b->rows, b->n, b->in_subgroup != 0, (const uint64_t*)scalars, m, (uint64_t*)out,
+                             workspace, workspace_bytes, (hipStream_t)stream),
            "kernel launch");
     return PA_OK;
 }
-int pa_g1_multiexp_prepared(const pa_g1_msm_bases* b, const pa_fr_repr* scalars, size_t m, pa_g1* out) {
+template <int G>
+int msm_prepared_host(const typename MsmAbi<G>::Bases* b, const pa_fr_repr* scalars, size_t m,
+                      typename MsmAbi<G>::Point* out) {
+    using Point = typename MsmAbi<G>::Point;
     if (!b || !out || (m && !scalars)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
     if (m > b->n) return fail(PA_ERR_INVALID_ARGUMENT, "more scalars than prepared bases");
     DevBuf ds, dout, dws;
     int rc;
     if ((rc = upload(ds, scalars, sizeof(pa_fr_repr) * m))) return rc;
-    PA_TRY(dout.alloc(sizeof(pa_g1)), "device scratch");
-    const size_t ws = pa::msm_prepared_workspace_bytes(m, b->in_subgroup != 0);
+    PA_TRY(dout.alloc(sizeof(Point)), "device scratch");
+    const size_t ws = pa::msm_prepared_workspace_bytes(m, b->in_subgroup != 0, G);
     PA_TRY(dws.alloc(ws), "device scratch");
-    if ((rc = pa_g1_multiexp_prepared_device(b, ds.as<pa_fr_repr>(), m, dout.as<pa_g1>(), dws.p, ws, call_stream())))
+    if ((rc = msm_prepared_device<G>(b, ds.as<pa_fr_repr>(), m, dout.as<Point>(), dws.p, ws, call_stream())))
         return rc;
     PA_TRY(call_sync(), "kernel execution");
-    return download(out, dout, sizeof(pa_g1));
+    return download(out, dout, sizeof(Point));
 }
 
 // k scalar vectors over the same prepared bases in one pipeline
-namespace {
 // what both batch entries refuse before touching memory; 0 = go on
-int batch_args(const pa_g1_msm_bases* b, size_t m, size_t k, unsigned flags) {
+int batch_args(const MsmBasesObj* b, int group, size_t m, size_t k, unsigned flags) {
     if (flags & ~PA_MSM_SCALARS_MONTGOMERY) return fail(PA_ERR_INVALID_ARGUMENT, "unknown PA_MSM_SCALARS_* flag bits");
     if (m > b->n) return fail(PA_ERR_INVALID_ARGUMENT, "more scalars than prepared bases");
-    if (!pa::msm_prepared_batch_fits(m, k, b->in_subgroup != 0))
+    if (!pa::msm_prepared_batch_fits(m, k, b->in_subgroup != 0, group))
         return fail(PA_ERR_INVALID_ARGUMENT,
                     "batch over the 32-bit item limit (k * windows * terms <= 2^32 - 1, k * windows * buckets < 2^32): "
                     "split it");
     return PA_OK;
 }
-}  // namespace
-size_t pa_g1_multiexp_prepared_batch_workspace_bytes(const pa_g1_msm_bases* b, size_t m, size_t k) {
-    return b && m <= b->n ? pa::msm_prepared_batch_workspace_bytes(m, k, b->in_subgroup != 0) : 0;
-}
-int pa_g1_multiexp_prepared_batch_device(const pa_g1_msm_bases* b, const void* scalars, size_t m, size_t k,
-                                         unsigned flags, pa_g1* out, void* workspace, size_t workspace_bytes,
-                                         void* stream) {
+template <int G>
+int msm_prepared_batch_device(const typename MsmAbi<G>::Bases* b, const void* scalars, size_t m, size_t k,
+                              unsigned flags, typename MsmAbi<G>::Point* out, void* workspace, size_t workspace_bytes,
+                              void* stream) {
     if (!b) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
     int rc;
-    if ((rc = batch_args(b, m, k, flags))) return rc;
+    if ((rc = batch_args(b, G, m, k, flags))) return rc;
     if (k == 0) return PA_OK;
     if (!out || (m && (!scalars || !workspace))) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
-    if (m && workspace_bytes < pa::msm_prepared_batch_workspace_bytes(m, k, b->in_subgroup != 0))
-        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_g1_multiexp_prepared_batch_workspace_bytes");
+    if (m && workspace_bytes < pa::msm_prepared_batch_workspace_bytes(m, k, b->in_subgroup != 0, G))
+        return fail(PA_ERR_INVALID_ARGUMENT, MsmAbi<G>::small_batch_ws);
     int dev = 0;
     PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
     if (dev != b->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the prepared bases");
-    PA_TRY(pa::launch_msm_prepared_g1_batch(b->rows, b->n, b->in_subgroup != 0, (const uint64_t*)scalars, m, k,
-                                            (flags & PA_MSM_SCALARS_MONTGOMERY) != 0, (uint64_t*)out, workspace,
-                                            workspace_bytes, (hipStream_t)stream),
+    PA_TRY(MsmAbi<G>::batch(b->rows, b->n, b->in_subgroup != 0, (const uint64_t*)scalars, m, k,
+                            (flags & PA_MSM_SCALARS_MONTGOMERY) != 0, (uint64_t*)out, workspace, workspace_bytes,
+                            (hipStream_t)stream),
            "kernel launch");
     return PA_OK;
 }
-int pa_g1_multiexp_prepared_batch(const pa_g1_msm_bases* b, const void* scalars, size_t m, size_t k, unsigned flags,
-                                  pa_g1* out) {
+template <int G>
+int msm_prepared_batch_host(const typename MsmAbi<G>::Bases* b, const void* scalars, size_t m, size_t k,
+                            unsigned flags, typename MsmAbi<G>::Point* out) {
+    using Point = typename MsmAbi<G>::Point;
     if (!b) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
     int rc;
-    if ((rc = batch_args(b, m, k, flags))) return rc;
+    if ((rc = batch_args(b, G, m, k, flags))) return rc;
     if (k == 0) return PA_OK;
     if (!out || (m && !scalars)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
     DevBuf ds, dout, dws;
     // k m rows fit: a batch within the item limit has k * m < 2^32
     if ((rc = upload(ds, scalars, sizeof(pa_fr_repr) * m * k))) return rc;
-    PA_TRY(dout.alloc(sizeof(pa_g1) * k), "device scratch");
-    const size_t ws = pa::msm_prepared_batch_workspace_bytes(m, k, b->in_subgroup != 0);
+    PA_TRY(dout.alloc(sizeof(Point) * k), "device scratch");
+    const size_t ws = pa::msm_prepared_batch_workspace_bytes(m, k, b->in_subgroup != 0, G);
     PA_TRY(dws.alloc(ws), "device scratch");
-    if ((rc = pa_g1_multiexp_prepared_batch_device(b, ds.p, m, k, flags, dout.as<pa_g1>(), dws.p, ws, call_stream())))
+    if ((rc = msm_prepared_batch_device<G>(b, ds.p, m, k, flags, dout.as<Point>(), dws.p, ws, call_stream())))
         return rc;
     PA_TRY(call_sync(), "kernel execution");
-    return download(out, dout, sizeof(pa_g1) * k);
+    return download(out, dout, sizeof(Point) * k);
 }
+}  // namespace
+}  // extern "C++"
+
+#define PA_MSM_PREPARED_ENTRIES(G)                                                                                     \
+    int pa_g##G##_msm_bases_prepare_device(const pa_g##G##_affine* bases, size_t n, void* stream,                      \
+                                           pa_g##G##_msm_bases** out) {                                                \
+        return msm_bases_prepare_device<G>(bases, n, stream, out);                                                     \
+    }                                                                                                                  \
+    int pa_g##G##_msm_bases_prepare(const pa_g##G##_affine* bases, size_t n, pa_g##G##_msm_bases** out) {              \
+        return msm_bases_prepare<G>(bases, n, out);                                                                    \
+    }                                                                                                                  \
+    size_t pa_g##G##_msm_bases_len(const pa_g##G##_msm_bases* b) { return b ? b->n : 0; }                              \
+    int pa_g##G##_msm_bases_in_subgroup(const pa_g##G##_msm_bases* b) { return b ? b->in_subgroup : 0; }               \
+    int pa_g##G##_msm_bases_free(pa_g##G##_msm_bases* b) { return msm_bases_free(b); }                                 \
+    size_t pa_g##G##_multiexp_prepared_workspace_bytes(const pa_g##G##_msm_bases* b, size_t m) {                       \
+        return b && m <= b->n ? pa::msm_prepared_workspace_bytes(m, b->in_subgroup != 0, G) : 0;                       \
+    }                                                                                                                  \
+    int pa_g##G##_multiexp_prepared_device(const pa_g##G##_msm_bases* b, const pa_fr_repr* scalars, size_t m,          \
+                                           pa_g##G* out, void* workspace, size_t workspace_bytes, void* stream) {      \
+        return msm_prepared_device<G>(b, scalars, m, out, workspace, workspace_bytes, stream);                         \
+    }                                                                                                                  \
+    int pa_g##G##_multiexp_prepared(const pa_g##G##_msm_bases* b, const pa_fr_repr* scalars, size_t m, pa_g##G* out) { \
+        return msm_prepared_host<G>(b, scalars, m, out);                                                               \
+    }                                                                                                                  \
+    size_t pa_g##G##_multiexp_prepared_batch_workspace_bytes(const pa_g##G##_msm_bases* b, size_t m, size_t k) {       \
+        return b && m <= b->n ? pa::msm_prepared_batch_workspace_bytes(m, k, b->in_subgroup != 0, G) : 0;              \
+    }                                                                                                                  \
+    int pa_g##G##_multiexp_prepared_batch_device(const pa_g##G##_msm_bases* b, const void* scalars, size_t m,          \
+                                                 size_t k, unsigned flags, pa_g##G* out, void* workspace,              \
+                                                 size_t workspace_bytes, void* stream) {                               \
+        return msm_prepared_batch_device<G>(b, scalars, m, k, flags, out, workspace, workspace_bytes, stream);         \
+    }                                                                                                                  \
+    int pa_g##G##_multiexp_prepared_batch(const pa_g##G##_msm_bases* b, const void* scalars, size_t m, size_t k,       \
+                                          unsigned flags, pa_g##G* out) {                                              \
+        return msm_prepared_batch_host<G>(b, scalars, m, k, flags, out);                                               \
+    }
+PA_MSM_PREPARED_ENTRIES(1)
+PA_MSM_PREPARED_ENTRIES(2)
+#undef PA_MSM_PREPARED_ENTRIES
 
 // ---- batched Fr NTT over a radix-2 evaluation domain (kernels_ntt.hip) ----
 // The object owns the power tables of its size on one device; the tile log

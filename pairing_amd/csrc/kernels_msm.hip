@@ -48,8 +48,12 @@
 // windows: the same msm_run with another digit kernel, term count and window
 // count (MsmJob).  Otherwise the 257-bit pipeline runs over rows [0, m).
 //
+// MSM over prepared G2 bases (launch_msm_prepare_g2 / launch_msm_prepared_g2):
+// the same over 56-word rows, with row n + i = (beta^2 x_i, -y_i) = x^2 Q_i
+// (kMsmBeta2): the split, the digit kernels and every stage are the G1 path's.
+//
 // A batch of k scalar vectors over the same prepared bases
-// (launch_msm_prepared_g1_batch) is the same pipeline over k W windows: vector
+// (launch_msm_prepared_g1_batch / _g2_batch) is the same pipeline over k W windows: vector
 // j's window w is window j W + w, its items gather the same rows, the window
 // parts are ranges of vectors and k_msm_horner_batch_q runs every vector's
 // Horner chain side by side.  The digit kernels take Montgomery Fr rows too.
@@ -160,6 +164,12 @@ static inline uint32_t msm_window_bits(size_t n) {
 // against 2.97 / 3.09 / 3.09 / 3.03 for c = 14 .. 17); then 15 (9 windows) and
 // from 2^21 virtual terms 17 (8 windows: 8 x 2^21 items against the plain
 // path's 17 x 2^20; 16 has 9 windows of 2^16 / 2 buckets, 6.75 ms against 6.03).
+// G2 keeps the rule: its additions cost three of G1's in the accumulation and
+// in the reduction alike, and the A/B of absolute values found the same optimum
+// (profiles/msm_g2_prepared/ab_single.txt), c = 10 / 11 / 12 / 13 / 14 / 15 / 16:
+// 2^14 terms 4.01 / 3.92 / 3.79 / 3.78 / 4.17 / 4.24 / 4.70 ms (the rule: 12),
+// 2^16 terms 5.78 / 5.06 / 4.85 / 4.12 / 4.98 / 4.95 / 6.14 ms (13),
+// 2^18 terms 10.41 / 8.27 / 8.76 / 6.85 / 7.78 / 8.29 / 8.78 ms (13).
 static inline uint32_t msm_window_bits_glv(size_t nt) {
     static const int env = (int)env_within("PA_MSM_GLV_C", 0, 4, 20);
     if (env) return (uint32_t)env;
@@ -180,6 +190,18 @@ static inline uint32_t msm_window_bits_glv(size_t nt) {
 // 2^12 terms, c = 8 / 9 / 10 / 11: 12.4 / 11.1 / 11.3 / 10.6 ms; 8 vectors of
 // 2^18 terms, c = 12 / 13 / 14 / 15: 12.6 / 11.8 / 11.7 / 13.0 ms.  So the rule
 // is the single call's, which also makes a batch of one vector its job.
+// G2 batches keep it too (profiles/msm_g2_prepared/ab_batch.txt, one part):
+// against c = 9 / 10 / 11 / 13 the rule measured, k x terms,
+//   2 x 2^18 (13): 11.84 ms against 15.65 / 14.36 / 12.07 / 11.86,
+//   2 x 2^16 (13): 5.03 against 5.77 / 5.32 / 5.29 / 5.03,
+//   4 x 2^16 (13): 8.21 against 8.52 / 8.28 / 8.82 / 8.28,
+//   8 x 2^16 (13): 12.74 against 13.74 / 13.41 / 12.47 / 12.73,
+//   4 x 2^14 (12): 4.00 against 4.14 / 4.01 / 4.12 / 3.60,
+//   16 x 2^14 (12): 9.91 against 8.21 / 8.61 / 8.82 / 10.98,
+//   16 x 2^12 (10): 3.74 against 3.91 / 3.73 / 4.19 / 6.78,
+//   64 x 2^12 (10): 8.95 against 9.06 / 9.34 / 11.31 / 21.92.
+// One shape, 16 x 2^14, would gain 17 % from c = 9 while 4 x 2^14 wants 13: no
+// rule in nt or k separates them, so none is added.
 static inline uint32_t msm_window_bits_batch(size_t nt) {
     static const int env = (int)env_within("PA_MSM_BATCH_C", 0, 4, 20);
     return env ? (uint32_t)env : msm_window_bits_glv(nt);
@@ -218,7 +240,10 @@ constexpr size_t kMsmLongSpan = 128;
 // 32 / 16 / 8 / 4 measured 6.32 / 6.06 / 6.18 / 6.03 / 6.07 ms at 2^20 terms and
 // 2.36 / 2.37 / 1.90 / 1.90 / 2.14 ms at 2^16: 8, and never below twice an
 // evenly filled bucket's span (msm_run), so that large MSMs whose every
-// bucket spans several chunks keep the one-lane fold.
+// bucket spans several chunks keep the one-lane fold.  G2 shares it: 4 / 8 /
+// 16 / 32 / 128 measured 3.69 / 3.78 / 4.11 / 4.66 / 8.02 ms at 2^14 G2 terms,
+// 4.08 / 4.10 / 4.12 / 5.49 / 5.42 at 2^16 and 6.85 / 6.86 / 6.87 / 8.27 / 8.08
+// at 2^18 (profiles/msm_g2_prepared/ab_single.txt): 4 and 8 within the spread.
 static size_t msm_long_span_glv() {
     static const size_t v = (size_t)env_within("PA_MSM_GLV_LONGSPAN", 8, 1, 4096);
     return v;
@@ -245,6 +270,12 @@ static uint32_t msm_parts(uint32_t W) {
 // accumulation: 1 / 2 / 4 / 8 parts measured 7.45 / 8.01 / 9.42 / 10.81 ms at
 // 16 vectors of 2^16 terms, 10.92 / 11.33 / 11.47 / 11.99 ms at 256 of 2^12 and
 // 11.35 / 11.85 / 12.76 / 15.57 ms at 8 of 2^18 (profiles/msm_prepared_batch/).
+// G2: 1 / 2 parts measured 11.84 / 13.57 ms at 2 vectors of 2^18 terms, 5.03 /
+// 5.24 at 2 of 2^16, 8.21 / 7.17 at 4 of 2^16, 12.74 / 13.75 at 8 of 2^16, 4.00 /
+// 4.39 at 4 of 2^14, 9.91 / 8.17 at 16 of 2^14, 3.74 / 4.01 at 16 of 2^12 and
+// 8.95 / 7.86 at 64 of 2^12; 3 and 4 parts never won
+// (profiles/msm_g2_prepared/ab_batch.txt).  Two parts win three shapes and
+// lose five with no pattern in k or the size: G2 stays at one.
 static uint32_t msm_parts_batch(size_t k) {
     static const uint32_t parts = (uint32_t)env_clamp("PA_MSM_BATCH_PARTS", 1, 1, kMsmMaxParts);
     return parts < k ? parts : (uint32_t)k;
@@ -956,22 +987,25 @@ __global__ void __launch_bounds__(64) k_msm_horner_q(const uint64_t* __restrict_
     store_jac_q(out, acc, lane == 0);
 }
 
-// The batch's Horner (G1): vector j of [j0, j1) on its own group of 4 quads,
-// four groups per wave, over its windows j W + w from the top down as
-// k_msm_horner_q does; the point goes to out + JW j.  A vector whose window
-// sums are all zero keeps the zero point it loaded.
-constexpr unsigned kHornerPerWave = 4;
+// The batch's Horner: vector j of [j0, j1) on its own group of quads (G1: 4
+// quads, four groups per wave; G2: 8 quads, two per wave), over its windows
+// j W + w from the top down as k_msm_horner_q does; the point goes to
+// out + JW j.  A vector whose window sums are all zero keeps the zero point
+// it loaded.
+template <int G> constexpr unsigned kHornerPerWave = G == 1 ? 4 : 2;
+template <int G>
 __global__ void __launch_bounds__(64) k_msm_horner_batch_q(const uint64_t* __restrict__ wsum, uint32_t stride,
                                                            uint32_t W, uint32_t c, size_t j0, size_t j1,
                                                            uint64_t* __restrict__ out) {
-    constexpr int NQ = 4, L = 4 * NQ, JW = Grp<1>::JW;
-    static_assert(64 / L == kHornerPerWave, "groups per wave");
+    constexpr int NQ = G == 1 ? 4 : 8, L = 4 * NQ, JW = Grp<G>::JW;
+    using E = typename std::conditional<G == 1, dq::Jq<dq::Q>, dq::Jq<dq::Q2>>::type;
+    static_assert(64 / L == kHornerPerWave<G>, "groups per wave");
     const int lane = threadIdx.x;
-    const size_t j = j0 + (size_t)blockIdx.x * kHornerPerWave + lane / L;
+    const size_t j = j0 + (size_t)blockIdx.x * kHornerPerWave<G> + lane / L;
     if (j >= j1) return;   // whole groups leave together
     const dq::Lc l = dq::lctx(lane, NQ);
     const uint64_t* ws = wsum + (size_t)JW * stride * (j * W);
-    dq::Jq<dq::Q> acc;
+    E acc;
     load_jac_q(acc, ws + (size_t)JW * stride * (W - 1), l);
 #pragma unroll 1
     for (int w = (int)W - 2; w >= 0; w--) {
@@ -979,7 +1013,7 @@ __global__ void __launch_bounds__(64) k_msm_horner_batch_q(const uint64_t* __res
 #pragma unroll 1
             for (uint32_t k = 0; k < c; k++) dq::jdbl<NQ>(acc, l);
         }
-        dq::Jq<dq::Q> x;
+        E x;
         load_jac_q(x, ws + (size_t)JW * stride * w, l);
         if (!dq::is_zero(x.z)) dq::jadd<NQ>(acc, dq::make_fixed<NQ>(x, l), l);
     }
@@ -1040,6 +1074,48 @@ __global__ void __launch_bounds__(256) k_msm_bases_fl2(const uint64_t* __restric
     for (int c = 0; c < 4; c++)
 #pragma unroll
         for (int k = 0; k < 14; k++) d[14 * c + k] = v[c].w[k] | (c == 0 && k == 13 && a.inf ? 0x80000000u : 0u);
+}
+
+// The prepared G2 rows (launch_msm_prepare_g2): row i as k_msm_bases_fl2 writes
+// it, row n + i = x^2 Q_i = (beta^2 x_i, -y_i) with beta^2 scaling both Fq
+// components of x; an infinity base flagged in both; the membership flags
+// ok[i] (launch_subgroup_check) counted into *bad.
+// kMsmBeta2 is the square of kMsmBeta (Montgomery words), the other primitive
+// cube root of unity in Fq.  On G1 (x, y) -> (beta x, y) multiplies by -x^2,
+// one root of l^2 + l + 1 = 0 mod r; on the twist's subgroup G2 the same map
+// multiplies by the other root, (-x^2)^2 = x^2 - 1, so the map that multiplies
+// by -x^2 there, the one the split s = q x^2 + rem needs, is the one with
+// beta^2 (tests/test_msm_g2_prepared.py checks it against the oracle).
+__constant__ const uint64_t kMsmBeta2[6] = {0xcd03c9e48671f071ULL, 0x5dab22461fcda5d2ULL, 0x587042afd3851b95ULL,
+                                            0x8eb60ebe01bacb9eULL, 0x03f97d6e83d050d2ULL, 0x18f0206554638741ULL};
+__global__ void __launch_bounds__(256) k_msm_bases_prepare_g2(const uint64_t* __restrict__ bases,
+                                                              const uint8_t* __restrict__ ok, size_t n,
+                                                              uint32_t* __restrict__ rows,
+                                                              uint32_t* __restrict__ bad) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Aff<Fq2> a;
+    load_aff(a, bases + (size_t)Grp<2>::AW * i);
+    Fq beta2, bx0, bx1, ny0, ny1;
+    fq_load(beta2, kMsmBeta2);
+    mul(bx0, a.x.c0, beta2);
+    mul(bx1, a.x.c1, beta2);
+    neg(ny0, a.y.c0);
+    neg(ny1, a.y.c1);
+    const F<1> v[4] = {fl_from_abi(a.x.c0), fl_from_abi(a.x.c1), fl_from_abi(a.y.c0), fl_from_abi(a.y.c1)};
+    const F<1> p[4] = {fl_from_abi(bx0), fl_from_abi(bx1), fl_from_abi(ny0), fl_from_abi(ny1)};
+    const uint32_t inf = a.inf ? 0x80000000u : 0u;
+    uint32_t* d = rows + 56 * i;
+    uint32_t* e = rows + 56 * (n + i);
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+        for (int k = 0; k < 14; k++) {
+            const uint32_t flag = c == 0 && k == 13 ? inf : 0u;
+            d[14 * c + k] = v[c].w[k] | flag;
+            e[14 * c + k] = p[c].w[k] | flag;
+        }
+    if (!ok[i]) atomicAdd(bad, 1u);
 }
 
 PA_DEV void msm_flush_fl2(uint32_t key, const FlJac2& acc, bool untouched, size_t j0, size_t k,
@@ -1242,22 +1318,22 @@ size_t msm_workspace_bytes(int group, size_t n) {
     if (msm_plan(p, group, n) != hipSuccess) return 0;
     return p.total;
 }
-size_t msm_prepared_rows_bytes(size_t n) { return 2 * n * 28 * sizeof(uint32_t); }
-size_t msm_prepared_workspace_bytes(size_t m, bool glv) {
+size_t msm_prepared_rows_bytes(size_t n, int group) { return 2 * n * (group == 1 ? 28 : 56) * sizeof(uint32_t); }
+size_t msm_prepared_workspace_bytes(size_t m, bool glv, int group) {
     if (m == 0) return 0;
     MsmPlan p;
-    if (msm_plan(p, 1, glv ? 2 * m : m, glv, false) != hipSuccess) return 0;
+    if (msm_plan(p, group, glv ? 2 * m : m, glv, false) != hipSuccess) return 0;
     return p.total;
 }
-bool msm_prepared_batch_fits(size_t m, size_t k, bool glv) {
+bool msm_prepared_batch_fits(size_t m, size_t k, bool glv, int group) {
     if (m == 0 || k == 0) return true;
     MsmPlan p;
-    return msm_plan(p, 1, glv ? 2 * m : m, glv, false, k) == hipSuccess && p.fits;
+    return msm_plan(p, group, glv ? 2 * m : m, glv, false, k) == hipSuccess && p.fits;
 }
-size_t msm_prepared_batch_workspace_bytes(size_t m, size_t k, bool glv) {
+size_t msm_prepared_batch_workspace_bytes(size_t m, size_t k, bool glv, int group) {
     if (m == 0 || k == 0) return 0;
     MsmPlan p;
-    if (msm_plan(p, 1, glv ? 2 * m : m, glv, false, k) != hipSuccess || !p.fits) return 0;
+    if (msm_plan(p, group, glv ? 2 * m : m, glv, false, k) != hipSuccess || !p.fits) return 0;
     return p.total;
 }
 
@@ -1294,7 +1370,7 @@ static hipError_t msm_side_streams(hipStream_t caller, hipStream_t out[2]) {
 }
 
 // What one MSM sums: `terms` scalars over affine ABI records converted per call
-// (bases; the plain entries), or over prepared lazy rows (rows, G1): the
+// (bases; the plain entries), or over prepared lazy rows (rows): the
 // 257-bit digits over rows [0, terms), or with glv the two virtual terms per
 // scalar over rows i and row_off + i.
 struct MsmJob {
@@ -1519,12 +1595,13 @@ struct MsmEvents {
 // default (msm_parts_batch).  With more, the caller's stream accumulates part
 // after part; the reduction and Horner grid of every part but the last run
 // behind it on the side streams, in turn.
-static hipError_t msm_schedule_batch(const MsmStages<1>& st, size_t k, uint64_t* out, hipStream_t s) {
+template <int G>
+static hipError_t msm_schedule_batch(const MsmStages<G>& st, size_t k, uint64_t* out, hipStream_t s) {
     const MsmPlan& p = st.p;
     const uint32_t parts = msm_parts_batch(k);
     auto horner = [&](size_t v0, size_t v1, hipStream_t hs) {
-        hipLaunchKernelGGL(k_msm_horner_batch_q, dim3(msm_blocks(v1 - v0, kHornerPerWave)), dim3(64), 0, hs, st.wsum,
-                           st.spw, p.W, p.c, v0, v1, out);
+        hipLaunchKernelGGL(k_msm_horner_batch_q<G>, dim3(msm_blocks(v1 - v0, kHornerPerWave<G>)), dim3(64), 0, hs,
+                           st.wsum, st.spw, p.W, p.c, v0, v1, out);
         return hipGetLastError();
     };
     hipError_t e;
@@ -1624,7 +1701,6 @@ static hipError_t msm_schedule_windows(const MsmStages<G>& st, uint64_t* out, hi
 template <int G>
 static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_bytes, hipStream_t s) {
     if (job.vectors == 0) return hipSuccess;
-    if (G != 1 && (job.rows || job.vectors > 1)) return hipErrorInvalidValue;   // prepared rows and batches are G1's
     if (job.terms == 0) {
         hipLaunchKernelGGL(k_jac_zero_out<G>, dim3(msm_blocks(job.vectors, 64)), dim3(64), 0, s, out, job.vectors);
         return hipGetLastError();
@@ -1640,8 +1716,7 @@ static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_
     if ((e = msm_sort_items(job, p, n, w, s)) != hipSuccess) return e;
     if ((e = msm_bounds_and_bases<G>(job, p, n, w, s)) != hipSuccess) return e;
     const MsmStages<G> st(p, w, n, job.glv);
-    if constexpr (G == 1)
-        if (job.vectors > 1) return msm_schedule_batch(st, job.vectors, out, s);
+    if (job.vectors > 1) return msm_schedule_batch<G>(st, job.vectors, out, s);
     return msm_schedule_windows<G>(st, out, s);
 }
 
@@ -1661,21 +1736,44 @@ hipError_t launch_msm_prepare_g1(const uint64_t* bases, const uint8_t* ok, size_
     return hipGetLastError();
 }
 
-hipError_t launch_msm_prepared_g1(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
-                                  uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream) {
-    if (len >= kMsmPreparedMax || m > len) return hipErrorInvalidValue;
-    const MsmJob job{nullptr, rows, scalars, m, len, glv};
-    return msm_run<1>(job, out, ws, ws_bytes, stream);
+hipError_t launch_msm_prepare_g2(const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows, uint32_t* bad,
+                                 hipStream_t stream) {
+    if (n >= kMsmPreparedMax) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess || n == 0) return e;
+    hipLaunchKernelGGL(k_msm_bases_prepare_g2, dim3(msm_blocks(n, 256)), dim3(256), 0, stream, bases, ok, n, rows,
+                       bad);
+    return hipGetLastError();
 }
 
-hipError_t launch_msm_prepared_g1_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
-                                        size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
-                                        hipStream_t stream) {
+// k vectors over the prepared rows of either group; k = 1 without mont is the single entry's job
+template <int G>
+static hipError_t msm_prepared(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m, size_t k,
+                               bool mont, uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream) {
     if (len >= kMsmPreparedMax || m > len) return hipErrorInvalidValue;
     MsmJob job{nullptr, rows, scalars, m, len, glv};
     job.vectors = k;
     job.mont = mont;
-    return msm_run<1>(job, out, ws, ws_bytes, stream);
+    return msm_run<G>(job, out, ws, ws_bytes, stream);
+}
+
+hipError_t launch_msm_prepared_g1(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
+                                  uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream) {
+    return msm_prepared<1>(rows, len, glv, scalars, m, 1, false, out, ws, ws_bytes, stream);
+}
+hipError_t launch_msm_prepared_g1_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
+                                        size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
+                                        hipStream_t stream) {
+    return msm_prepared<1>(rows, len, glv, scalars, m, k, mont, out, ws, ws_bytes, stream);
+}
+hipError_t launch_msm_prepared_g2(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
+                                  uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream) {
+    return msm_prepared<2>(rows, len, glv, scalars, m, 1, false, out, ws, ws_bytes, stream);
+}
+hipError_t launch_msm_prepared_g2_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
+                                        size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
+                                        hipStream_t stream) {
+    return msm_prepared<2>(rows, len, glv, scalars, m, k, mont, out, ws, ws_bytes, stream);
 }
 
 hipError_t launch_scalar_mul(int group, int projective, const uint64_t* p, const uint64_t* scalars, size_t n,

@@ -18,23 +18,29 @@ size_t msm_workspace_bytes(int group, size_t n);
 hipError_t launch_msm(int group, const uint64_t* bases, const uint64_t* scalars, size_t n, uint64_t* out, void* ws,
                       size_t ws_bytes, hipStream_t stream);
 
-// ---- G1 MSM over prepared bases ----
-// Prepared rows: 2n records of 28 u32 (the lazy 14 x 28-bit x, y the bucket
+// ---- MSM over prepared bases ----
+// Prepared rows, G1: 2n records of 28 u32 (the lazy 14 x 28-bit x, y the bucket
 // accumulation gathers; infinity in bit 31 of x's top limb), row i = P_i, row
-// n + i = -phi(P_i) = (beta x_i, -y_i).  n < kMsmPreparedMax: a row index and
-// a sign share 32 bits.
+// n + i = -phi(P_i) = (beta x_i, -y_i).  G2: 2n records of 56 u32 (x.c0, x.c1,
+// y.c0, y.c1; infinity in bit 31 of x.c0's top limb), row i = Q_i, row n + i =
+// x^2 Q_i = (beta^2 x_i, -y_i).  n < kMsmPreparedMax: a row index and a sign
+// share 32 bits.  `group` (1: G1, 2: G2) sizes the rows and the workspaces.
 constexpr size_t kMsmPreparedMax = (size_t)1 << 30;
-size_t msm_prepared_rows_bytes(size_t n);
+size_t msm_prepared_rows_bytes(size_t n, int group = 1);
 // rows from the affine records; *bad = number of i with ok[i] == 0 (the
 // membership flags of launch_subgroup_check over the same records)
 hipError_t launch_msm_prepare_g1(const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows, uint32_t* bad,
                                  hipStream_t stream);
+hipError_t launch_msm_prepare_g2(const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows, uint32_t* bad,
+                                 hipStream_t stream);
 // out[0] = sum_{i < m} scalars[i] * P_i over the rows of `len` prepared bases.
-// glv (every base in G1): s = q x^2 + rem, the two halves over rows i and
-// len + i in ceil(130 / c) windows; otherwise the 257-bit pipeline over rows
-// [0, m).  `ws` holds msm_prepared_workspace_bytes(m, glv) bytes.
-size_t msm_prepared_workspace_bytes(size_t m, bool glv);
+// glv (every base in the subgroup): s = q x^2 + rem, the two halves over rows i
+// and len + i in ceil(130 / c) windows; otherwise the 257-bit pipeline over rows
+// [0, m).  `ws` holds msm_prepared_workspace_bytes(m, glv, group) bytes.
+size_t msm_prepared_workspace_bytes(size_t m, bool glv, int group = 1);
 hipError_t launch_msm_prepared_g1(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
+                                  uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream);
+hipError_t launch_msm_prepared_g2(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
                                   uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream);
 
 // out[j] = sum_{i < m} scalars[j m + i] * P_i for j < k: k vectors end to end
@@ -43,9 +49,12 @@ hipError_t launch_msm_prepared_g1(const uint32_t* rows, size_t len, bool glv, co
 // and keys are 32-bit: msm_prepared_batch_fits says whether k W nt <= 2^32 - 1
 // and k W B < 2^32 hold for the plan of (m, k); a batch that does not fit has
 // workspace size 0 and is refused.
-bool msm_prepared_batch_fits(size_t m, size_t k, bool glv);
-size_t msm_prepared_batch_workspace_bytes(size_t m, size_t k, bool glv);
+bool msm_prepared_batch_fits(size_t m, size_t k, bool glv, int group = 1);
+size_t msm_prepared_batch_workspace_bytes(size_t m, size_t k, bool glv, int group = 1);
 hipError_t launch_msm_prepared_g1_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
+                                        size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
+                                        hipStream_t stream);
+hipError_t launch_msm_prepared_g2_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
                                         size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
                                         hipStream_t stream);
 

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, FrNttDomain, G1MsmBases, _lib, call, csr_offsets, msm_scalars, ntt_mode
+from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, FrNttDomain, G1MsmBases, G2MsmBases, _lib, call, csr_offsets, msm_bases, msm_scalars, ntt_mode
 
 
 def _stream_ptr(stream):
@@ -349,44 +349,91 @@ def multiexp(group, bases, scalars, out, workspace, stream=None):
          _stream_ptr(stream))
 
 
+# the prepared entries of both groups: (handle class, affine width, Jacobian width, the preparing function)
+_MSM_GROUPS = {1: (G1MsmBases, W_G1A, W_G1, "msm_prepare"), 2: (G2MsmBases, W_G2A, W_G2, "g2_msm_prepare")}
+
+
+def _msm_prepare(group, bases, stream):
+    cls, aw, _, _ = _MSM_GROUPS[group]
+    n = bases.shape[0]
+    h = ctypes.c_void_p(0)
+    call("pa_g%d_msm_bases_prepare_device" % group, _dptr(bases, aw, "bases"), n, _stream_ptr(stream),
+         ctypes.byref(h))
+    return cls._adopt(h)
+
+
+def _msm_handle(group, prepared, m):
+    """the handle of this group's live object, after checking that m terms fit"""
+    cls, _, _, maker = _MSM_GROUPS[group]
+    return msm_bases(prepared, cls, maker).check_terms(m)
+
+
+def _multiexp_prepared_workspace(group, prepared, m, device):
+    m = int(m)
+    h = _msm_handle(group, prepared, m)
+    nbytes = int(getattr(_lib, "pa_g%d_multiexp_prepared_workspace_bytes" % group)(h, m))
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
+def _multiexp_prepared(group, prepared, scalars, out, workspace, stream):
+    m = scalars.shape[0]
+    h = _msm_handle(group, prepared, m)
+    _rows(out, 1, "out")
+    call("pa_g%d_multiexp_prepared_device" % group, h, _dptr(scalars, 4, "scalars"), m,
+         _dptr(out, _MSM_GROUPS[group][2], "out"), ctypes.c_void_p(workspace.data_ptr()), workspace.numel(),
+         _stream_ptr(stream))
+
+
+def _multiexp_prepared_batch_workspace(group, prepared, m, k, device):
+    m, k = int(m), int(k)
+    if k < 0:
+        raise ValueError("k must not be negative, got %d" % k)
+    h = _msm_handle(group, prepared, m)
+    nbytes = int(getattr(_lib, "pa_g%d_multiexp_prepared_batch_workspace_bytes" % group)(h, m, k))
+    if nbytes == 0 and m and k:
+        raise ValueError("a batch of %d vectors of %d terms is over the 32-bit item limit: split it" % (k, m))
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
+def _multiexp_prepared_batch(group, prepared, scalars, m, k, out, workspace, montgomery, stream):
+    m, k = int(m), int(k)
+    cls, _, _, maker = _MSM_GROUPS[group]
+    msm_bases(prepared, cls, maker)
+    flags = msm_scalars(montgomery)
+    h = prepared.check_terms(m)
+    if k < 0:
+        raise ValueError("k must not be negative, got %d" % k)
+    _rows(scalars, k * m, "scalars")
+    _rows(out, k, "out")
+    call("pa_g%d_multiexp_prepared_batch_device" % group, h, _dptr(scalars, 4, "scalars"), m, k, flags,
+         _dptr(out, _MSM_GROUPS[group][2], "out"), ctypes.c_void_p(workspace.data_ptr()), workspace.numel(),
+         _stream_ptr(stream))
+
+
 def msm_prepare(bases, stream=None):
     """Prepare G1 multiexp bases resident in HBM ((n, 13) affine records) once:
     the membership check and the conversion the plain multiexp repeats per call.
     Synchronizes the stream.  Returns a G1MsmBases (len, in_subgroup, close())
     tied to the tensor's device; `bases` may be released afterwards."""
-    n = bases.shape[0]
-    h = ctypes.c_void_p(0)
-    call("pa_g1_msm_bases_prepare_device", _dptr(bases, W_G1A, "bases"), n, _stream_ptr(stream), ctypes.byref(h))
-    return G1MsmBases._adopt(h)
+    return _msm_prepare(1, bases, stream)
 
 
 def multiexp_prepared_workspace(prepared, m, device):
     """A device workspace sized for multiexp_prepared over the first m prepared bases."""
-    nbytes = int(_lib.pa_g1_multiexp_prepared_workspace_bytes(prepared.check_terms(int(m)), int(m)))
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+    return _multiexp_prepared_workspace(1, prepared, m, device)
 
 
 def multiexp_prepared(prepared, scalars, out, workspace, stream=None):
     """out (1, 18) = sum_i scalars[i] * P_i over the first m = len(scalars) prepared
     bases (FrRepr (m, 4)), equal as a point to multiexp(1, ...) over the same bases."""
-    m = scalars.shape[0]
-    h = prepared.check_terms(m)
-    _rows(out, 1, "out")
-    call("pa_g1_multiexp_prepared_device", h, _dptr(scalars, 4, "scalars"), m, _dptr(out, W_G1, "out"),
-         ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
+    _multiexp_prepared(1, prepared, scalars, out, workspace, stream)
 
 
 def multiexp_prepared_batch_workspace(prepared, m, k, device):
     """A device workspace sized for multiexp_prepared_batch: k vectors over the first m
     prepared bases.  A batch over the 32-bit item limit (include/pairing_amd.h) is a
     ValueError: split it."""
-    m, k = int(m), int(k)
-    if k < 0:
-        raise ValueError("k must not be negative, got %d" % k)
-    nbytes = int(_lib.pa_g1_multiexp_prepared_batch_workspace_bytes(prepared.check_terms(m), m, k))
-    if nbytes == 0 and m and k:
-        raise ValueError("a batch of %d vectors of %d terms is over the 32-bit item limit: split it" % (k, m))
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+    return _multiexp_prepared_batch_workspace(1, prepared, m, k, device)
 
 
 def multiexp_prepared_batch(prepared, scalars, m, k, out, workspace, montgomery=False, stream=None):
@@ -394,17 +441,34 @@ def multiexp_prepared_batch(prepared, scalars, m, k, out, workspace, montgomery=
     k vectors end to end in `scalars` ((k * m, 4); FrRepr rows, or with montgomery=True
     the Montgomery Fr rows fr_ntt writes), each equal as a point to multiexp_prepared
     over that vector.  Nothing is allocated or read back."""
-    if not isinstance(prepared, G1MsmBases):
-        raise ValueError("prepared must come from msm_prepare")
-    m, k = int(m), int(k)
-    flags = msm_scalars(montgomery)
-    h = prepared.check_terms(m)
-    if k < 0:
-        raise ValueError("k must not be negative, got %d" % k)
-    _rows(scalars, k * m, "scalars")
-    _rows(out, k, "out")
-    call("pa_g1_multiexp_prepared_batch_device", h, _dptr(scalars, 4, "scalars"), m, k, flags,
-         _dptr(out, W_G1, "out"), ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
+    _multiexp_prepared_batch(1, prepared, scalars, m, k, out, workspace, montgomery, stream)
+
+
+def g2_msm_prepare(bases, stream=None):
+    """msm_prepare for G2 bases ((n, 25) affine records): returns a G2MsmBases.  The G1
+    and G2 functions take only their own group's object (ValueError otherwise)."""
+    return _msm_prepare(2, bases, stream)
+
+
+def g2_multiexp_prepared_workspace(prepared, m, device):
+    """A device workspace sized for g2_multiexp_prepared over the first m prepared bases."""
+    return _multiexp_prepared_workspace(2, prepared, m, device)
+
+
+def g2_multiexp_prepared(prepared, scalars, out, workspace, stream=None):
+    """out (1, 36) = sum_i scalars[i] * Q_i over the first m = len(scalars) prepared G2
+    bases (FrRepr (m, 4)), equal as a point to multiexp(2, ...) over the same bases."""
+    _multiexp_prepared(2, prepared, scalars, out, workspace, stream)
+
+
+def g2_multiexp_prepared_batch_workspace(prepared, m, k, device):
+    """multiexp_prepared_batch_workspace for prepared G2 bases."""
+    return _multiexp_prepared_batch_workspace(2, prepared, m, k, device)
+
+
+def g2_multiexp_prepared_batch(prepared, scalars, m, k, out, workspace, montgomery=False, stream=None):
+    """multiexp_prepared_batch over prepared G2 bases: out (k, 36)."""
+    _multiexp_prepared_batch(2, prepared, scalars, m, k, out, workspace, montgomery, stream)
 
 
 def wnaf_exact_workspace(group, n, window, fixed_scalar, device):
