@@ -544,6 +544,39 @@ int pa_fr_ntt(const pa_fr_ntt_domain *d, int mode, const pa_fr *in, pa_fr *out, 
 int pa_fr_ntt_device(const pa_fr_ntt_domain *d, int mode, const pa_fr *in, pa_fr *out, size_t batch,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* The quotient of a Groth16 proof over the domain: from the evaluations of A, B
+ * and C the coefficients of h = (A B - C) / Z, Z = X^n - 1, as
+ *   h_j = coset_inverse( (coset_forward(inverse(a_j)) * coset_forward(inverse(b_j))
+ *                         - coset_forward(inverse(c_j))) * (g^n - 1)^-1 )
+ * for each of `batch` triples: a, b and c are three arrays laid out as the
+ * transforms lay out polynomials, out gets n Montgomery coefficient rows per
+ * polynomial, canonical, natural order, bit-identical to that composition of
+ * pa_fr_ntt, pa_fr_mul_batch and pa_fr_sub_batch (for any input; where c = a * b
+ * on the domain, row n - 1 is zero).  It runs as 3 x passes launches: a pass of
+ * the first two transforms covers a, b and c in one grid, the last transform
+ * forms A B - C as it loads, and the inverse transforms' n^-1 and 1 / Z ride on
+ * the coset factors of a's and c's forward transforms (two multiplications
+ * per point fewer than the seven transforms on their own).
+ * log_n = 0 is one elementwise launch of (a b - c) / 6.
+ *
+ * out may be exactly a, b or c; a, b and c may be one another (a == b gives
+ * a^2 - c); inputs that out does not alias are only read.  A NULL domain, a
+ * NULL pointer with batch > 0, out overlapping an input partly, a workspace
+ * smaller than pa_fr_ntt_quotient_workspace_bytes(d, batch), or a stream on
+ * another device return a code before anything is launched; batch = 0 is a
+ * no-op.  The workspace is 3 batch n 32 bytes for a one-pass domain (the coset
+ * evaluations), 6 batch n 32 for several passes, 0 for log_n = 0, and must not
+ * overlap a, b, c or out.  The query returns 0 for a NULL domain and when the
+ * 3 batch polynomials of a pass do not fit a grid: the entries then return
+ * PA_ERR_INVALID_ARGUMENT and the caller splits the batch.  The device entry
+ * allocates nothing, does not synchronize, reads nothing back and can be
+ * captured into a HIP graph (one chain of launches). */
+size_t pa_fr_ntt_quotient_workspace_bytes(const pa_fr_ntt_domain *d, size_t batch);
+int pa_fr_ntt_quotient(const pa_fr_ntt_domain *d, const pa_fr *a, const pa_fr *b, const pa_fr *c, pa_fr *out,
+                       size_t batch);   /* host memory */
+int pa_fr_ntt_quotient_device(const pa_fr_ntt_domain *d, const pa_fr *a, const pa_fr *b, const pa_fr *c, pa_fr *out,
+                              size_t batch, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- device-resident variants (pointers are device memory) ---- */
 int pa_g1_decode_batch_device(const uint8_t *enc, size_t n, int compressed, int checked, pa_g1_affine *out,
                               uint8_t *status, void *stream);

@@ -698,6 +698,18 @@ public:
     std::vector<pa_fr> icoset_fft(const std::vector<pa_fr>& a) const {
         return run(PA_NTT_COSET_INVERSE, a, "FrNttDomain::icoset_fft");
     }
+    // the coefficients of h = (A B - C) / (X^n - 1) from the evaluations a, b, c of each polynomial triple
+    // (pa_fr_ntt_quotient): icoset_fft((coset_fft(ifft(a)) * coset_fft(ifft(b)) - coset_fft(ifft(c))) / (g^n - 1))
+    std::vector<pa_fr> quotient(const std::vector<pa_fr>& a, const std::vector<pa_fr>& b,
+                                const std::vector<pa_fr>& c) const {
+        const char* what = "FrNttDomain::quotient";
+        if (a.size() != b.size() || a.size() != c.size())
+            throw std::invalid_argument(std::string(what) + ": a, b and c differ in length");
+        if (a.size() % size()) throw std::invalid_argument(std::string(what) + ": rows are not a multiple of the domain");
+        std::vector<pa_fr> out(a.size());
+        if (!a.empty()) check(pa_fr_ntt_quotient(h_, a.data(), b.data(), c.data(), out.data(), a.size() / size()), what);
+        return out;
+    }
 
 private:
     std::vector<pa_fr> run(int mode, const std::vector<pa_fr>& a, const char* what) const {

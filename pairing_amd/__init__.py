@@ -35,7 +35,7 @@ __all__ = [
     "g1_affine_mul", "g2_affine_mul", "g1_mul_assign", "g2_mul_assign", "g1_multiexp", "g2_multiexp",
     "G1MsmBases", "g1_msm_prepare", "g1_multiexp_prepared", "g1_multiexp_prepared_batch",
     "G2MsmBases", "g2_msm_prepare", "g2_multiexp_prepared", "g2_multiexp_prepared_batch",
-    "FrNttDomain", "fr_ntt_domain", "fr_ntt",
+    "FrNttDomain", "fr_ntt_domain", "fr_ntt", "fr_ntt_quotient",
     "g1_eq", "g2_eq", "g1_double", "g2_double", "g1_add", "g2_add", "g1_add_mixed", "g2_add_mixed", "g1_negate", "g2_negate",
     "g1_sub", "g2_sub", "g1_into_affine", "g2_into_affine", "g1_into_projective", "g2_into_projective",
     "g2_batch_normalization", "g2_wnaf_fixed_base",
@@ -712,6 +712,27 @@ def fr_ntt(domain, a, mode="forward"):
     out = np.zeros_like(a)
     if batch:
         call("pa_fr_ntt", h, m, ptr(a), ptr(out), batch)
+    return out
+
+
+def fr_ntt_quotient(domain, a, b, c):
+    """The quotient of a proof over the domain, as a new (batch * n, 4) array: from
+    the evaluations a, b, c of each polynomial triple (three arrays laid out as
+    fr_ntt's), the n coefficient rows of h = (A B - C) / (X^n - 1), that is
+    coset_inverse((coset_forward(inverse(a)) * coset_forward(inverse(b))
+    - coset_forward(inverse(c))) / (g^n - 1)), bit for bit.  Where c = a * b on
+    the domain, row n - 1 of every polynomial is zero."""
+    if not isinstance(domain, FrNttDomain):
+        raise ValueError("domain must come from fr_ntt_domain")
+    domain.handle()   # a closed object is rejected first
+    a, b, c = (as_rows(x, W_FR, name) if len(x) else np.zeros((0, W_FR), np.uint64)
+               for x, name in ((a, "a"), (b, "b"), (c, "c")))
+    if a.shape != b.shape or a.shape != c.shape:
+        raise ValueError("a, b and c must have the same shape, got %s, %s and %s" % (a.shape, b.shape, c.shape))
+    h, batch = domain.check_rows(a.shape[0])
+    out = np.zeros_like(a)
+    if batch:
+        call("pa_fr_ntt_quotient", h, ptr(a), ptr(b), ptr(c), ptr(out), batch)
     return out
 
 

@@ -181,6 +181,9 @@ _SIGS = {
     "pa_fr_ntt_workspace_bytes": [_P, _N],            # returns size_t (below)
     "pa_fr_ntt": [_P, ctypes.c_int, _P, _P, _N],
     "pa_fr_ntt_device": [_P, ctypes.c_int, _P, _P, _N, _P, _N, _P],
+    "pa_fr_ntt_quotient_workspace_bytes": [_P, _N],   # returns size_t (below)
+    "pa_fr_ntt_quotient": [_P, _P, _P, _P, _P, _N],
+    "pa_fr_ntt_quotient_device": [_P, _P, _P, _P, _P, _N, _P, _N, _P],
 }
 for _g in (1, 2):
     for _op in ("double", "negate", "into_affine", "into_projective"):
@@ -237,7 +240,8 @@ _lib.pa_multi_pairing_batch_workspace_bytes.restype = ctypes.c_size_t
 _lib.pa_fr_ntt_domain_free.restype = None
 for _name in ("pa_fr_ntt_domain_log_n", "pa_fr_ntt_domain_passes", "pa_fr_ntt_domain_tile_log", "pa_fr_ntt_max_log_n"):
     getattr(_lib, _name).restype = ctypes.c_uint
-for _name in ("pa_fr_ntt_domain_bytes", "pa_fr_ntt_polys_per_workgroup", "pa_fr_ntt_workspace_bytes"):
+for _name in ("pa_fr_ntt_domain_bytes", "pa_fr_ntt_polys_per_workgroup", "pa_fr_ntt_workspace_bytes",
+              "pa_fr_ntt_quotient_workspace_bytes"):
     getattr(_lib, _name).restype = ctypes.c_size_t
 
 
@@ -483,6 +487,10 @@ class FrNttDomain:
     def workspace_bytes(self, batch):
         """pa_fr_ntt_workspace_bytes(domain, batch): 0 for a one-pass domain"""
         return int(_lib.pa_fr_ntt_workspace_bytes(self.handle(), int(batch)))
+
+    def quotient_workspace_bytes(self, batch):
+        """pa_fr_ntt_quotient_workspace_bytes(domain, batch): 3 or 6 arrays of batch polynomials, 0 for log_n = 0"""
+        return int(_lib.pa_fr_ntt_quotient_workspace_bytes(self.handle(), int(batch)))
 
     def close(self):
         h, self._handle = self._handle, None

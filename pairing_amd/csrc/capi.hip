@@ -1914,6 +1914,67 @@ int pa_fr_ntt(const pa_fr_ntt_domain* d, int mode, const pa_fr* in, pa_fr* out, 
     return download(out, da, bytes);
 }
 
+// the quotient h = (A B - C) / Z of a proof over the domain (launch_ntt_quotient)
+size_t pa_fr_ntt_quotient_workspace_bytes(const pa_fr_ntt_domain* d, size_t batch) {
+    return d && pa::ntt_quotient_fits(d->layout, batch) ? pa::ntt_quotient_workspace_bytes(d->layout, batch) : 0;
+}
+
+namespace {
+// the checks of both quotient entries; the pointers are only compared
+int ntt_quotient_check(const pa_fr_ntt_domain* d, const pa_fr* a, const pa_fr* b, const pa_fr* c, pa_fr* out,
+                       size_t batch) {
+    if (!d) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (batch == 0) return PA_OK;
+    if (!a || !b || !c || !out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!pa::ntt_quotient_fits(d->layout, batch))
+        return fail(PA_ERR_INVALID_ARGUMENT,
+                    "NTT quotient batch too large (a pass over a, b and c would exceed a grid): split the batch");
+    const size_t bytes = (batch << d->layout.log_n) * sizeof(pa_fr);
+    const uintptr_t o = (uintptr_t)out;
+    const pa_fr* ins[3] = {a, b, c};
+    for (const pa_fr* in : ins) {
+        const uintptr_t i = (uintptr_t)in;
+        if (i != o && i < o + bytes && o < i + bytes)
+            return fail(PA_ERR_INVALID_ARGUMENT, "NTT quotient output overlaps an input partially");
+    }
+    return PA_OK;
+}
+}  // namespace
+
+int pa_fr_ntt_quotient_device(const pa_fr_ntt_domain* d, const pa_fr* a, const pa_fr* b, const pa_fr* c, pa_fr* out,
+                              size_t batch, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = ntt_quotient_check(d, a, b, c, out, batch)) return rc;
+    if (batch == 0) return PA_OK;
+    const size_t need = pa::ntt_quotient_workspace_bytes(d->layout, batch);
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_fr_ntt_quotient_workspace_bytes");
+    int dev = 0;
+    PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
+    if (dev != d->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the NTT domain");
+    PA_TRY(pa::launch_ntt_quotient(d->layout, d->tables, (const uint64_t*)a, (const uint64_t*)b, (const uint64_t*)c,
+                                   (uint64_t*)out, batch, workspace, (hipStream_t)stream),
+           "kernel launch");
+    return PA_OK;
+}
+int pa_fr_ntt_quotient(const pa_fr_ntt_domain* d, const pa_fr* a, const pa_fr* b, const pa_fr* c, pa_fr* out,
+                       size_t batch) {
+    if (int rc = ntt_quotient_check(d, a, b, c, out, batch)) return rc;
+    if (batch == 0) return PA_OK;
+    DevBuf da, db, dc, dws;
+    int rc;
+    const size_t bytes = (batch << d->layout.log_n) * sizeof(pa_fr);
+    if ((rc = upload(da, a, bytes))) return rc;
+    if ((rc = upload(db, b, bytes))) return rc;
+    if ((rc = upload(dc, c, bytes))) return rc;
+    const size_t ws = pa::ntt_quotient_workspace_bytes(d->layout, batch);
+    PA_TRY(dws.alloc(ws), "device scratch");
+    if ((rc = pa_fr_ntt_quotient_device(d, da.as<pa_fr>(), db.as<pa_fr>(), dc.as<pa_fr>(), da.as<pa_fr>(), batch, dws.p,
+                                        ws, call_stream())))
+        return rc;
+    PA_TRY(call_sync(), "kernel execution");
+    return download(out, da, bytes);
+}
+
 // ---- CurveProjective / CurveAffine surface, G1 and G2 (kernels_group.hip) ----
 namespace {
 constexpr size_t jac_bytes(int group) { return group == 1 ? sizeof(pa_g1) : sizeof(pa_g2); }

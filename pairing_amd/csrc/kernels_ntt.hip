@@ -33,6 +33,11 @@
 // the last round of a one-launch transform) would be 4- to 16-way under it
 // from 2^8 points up and has a swizzle of its own (ntt_swz): two-way at worst.
 // Every exchange of every tile shape is enumerated in DESIGN.md, "Fr NTT".
+//
+// The quotient of a proof, h = (A B - C) / Z from evaluations (launch_ntt_quotient),
+// is seven of these transforms in 3 x passes launches: k_ntt_pass3 runs a pass
+// over a, b and c in one grid, and its fused form loads A B - C as the first
+// round of the last transform; the constants ride on coset tables.
 #include "fr.h"
 #include "launch.h"
 
@@ -98,8 +103,11 @@ struct NttTile {
 
 // One round: the stages of row-index bits [lo, lo + R) on the 2^R rows a
 // thread holds, for every group of rows of the workgroup.
-template <int R>
-PA_DEV void ntt_round(const NttPass& a, const NttTile& tile, uint32_t* lds, uint32_t lo, bool first, bool last) {
+// F (the quotient's last transform): the first round loads in * fb - fc, the
+// rows of three arrays at one index, where the plain pass loads `in`.
+template <int R, bool F>
+PA_DEV void ntt_round(const NttPass& a, const NttTile& tile, uint32_t* lds, uint32_t lo, bool first, bool last,
+                      const uint64_t* fb, const uint64_t* fc) {
     constexpr int M = 1 << R;
     const uint32_t t = a.t, cb = a.cbits;
     const uint32_t elems = 1u << (t + cb);
@@ -126,6 +134,13 @@ PA_DEV void ntt_round(const NttPass& a, const NttTile& tile, uint32_t* lds, uint
                 const size_t idx = tile.in_base + (size_t)x * tile.sa_in + (size_t)c * tile.sc_in;
                 if (live) {
                     fr_load(v[m], a.in + 4 * idx);
+                    if constexpr (F) {
+                        Fr y;
+                        fr_load(y, fb + 4 * idx);
+                        v[m] = ntt_mul(v[m], y);
+                        fr_load(y, fc + 4 * idx);
+                        fr_sub(v[m], v[m], y);
+                    }
                     if (a.pre_coset) v[m] = ntt_mul(v[m], ntt_power(a.glo, a.ghi, (uint32_t)idx & nmask, a.split, two));
                 } else {
                     fr_zero(v[m]);
@@ -189,9 +204,9 @@ PA_DEV void ntt_round(const NttPass& a, const NttTile& tile, uint32_t* lds, uint
     }
 }
 
-__global__ void __launch_bounds__(kNttThreads, 2) k_ntt_pass(const NttPass a) {
-    extern __shared__ uint32_t ntt_lds[];
-    const size_t wg = blockIdx.x;
+// One workgroup's tile of a pass: `wg` counts the tiles of one array.
+template <bool F>
+PA_DEV void ntt_pass_tile(const NttPass& a, size_t wg, uint32_t* ntt_lds, const uint64_t* fb, const uint64_t* fc) {
     const uint32_t t = a.t, cb = a.cbits;
     NttTile tile;
     tile.r0 = 0;
@@ -232,14 +247,67 @@ __global__ void __launch_bounds__(kNttThreads, 2) k_ntt_pass(const NttPass a) {
         const uint32_t r = rem == 4 ? 2u : (rem < 3 ? rem : 3u);
         const uint32_t lo = rem - r;
         if (r == 3)
-            ntt_round<3>(a, tile, ntt_lds, lo, first, lo == 0);
+            ntt_round<3, F>(a, tile, ntt_lds, lo, first, lo == 0, fb, fc);
         else if (r == 2)
-            ntt_round<2>(a, tile, ntt_lds, lo, first, lo == 0);
+            ntt_round<2, F>(a, tile, ntt_lds, lo, first, lo == 0, fb, fc);
         else
-            ntt_round<1>(a, tile, ntt_lds, lo, first, lo == 0);
+            ntt_round<1, F>(a, tile, ntt_lds, lo, first, lo == 0, fb, fc);
         rem = lo;
         first = false;
         if (rem) __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(kNttThreads, 2) k_ntt_pass(const NttPass a) {
+    extern __shared__ uint32_t ntt_lds[];
+    ntt_pass_tile<false>(a, blockIdx.x, ntt_lds, nullptr, nullptr);
+}
+
+// The quotient's launches (launch_ntt_quotient): the pass `p` over the arrays
+// in[i] -> out[i], each with its own tiles (a batch tail per array in a
+// one-launch transform) and its own low table of coset factors (which is
+// where each array's constant rides).
+struct NttPass3 {
+    NttPass p;   // in, out and glo are taken from the arrays below
+    const uint64_t* in[3];
+    uint64_t* out[3];
+    const uint64_t* glo[3];
+    uint32_t tiles;   // workgroups per array
+};
+
+// F = false: three arrays, a grid of 3 x tiles.  F = true: one transform whose
+// first round loads in[0] * in[1] - in[2] and writes out[0], a grid of `tiles`.
+template <bool F>
+__global__ void __launch_bounds__(kNttThreads, 2) k_ntt_pass3(const NttPass3 q) {
+    extern __shared__ uint32_t ntt_lds[];
+    NttPass a = q.p;
+    uint32_t wg = blockIdx.x;
+    if constexpr (F) {
+        a.in = q.in[0], a.out = q.out[0], a.glo = q.glo[0];
+    } else {
+        const uint32_t arr = wg / q.tiles;   // the same for the whole workgroup: selects, no indexed copy of q
+        wg -= arr * q.tiles;
+        a.in = arr == 0 ? q.in[0] : (arr == 1 ? q.in[1] : q.in[2]);
+        a.out = arr == 0 ? q.out[0] : (arr == 1 ? q.out[1] : q.out[2]);
+        a.glo = arr == 0 ? q.glo[0] : (arr == 1 ? q.glo[1] : q.glo[2]);
+    }
+    ntt_pass_tile<F>(a, wg, ntt_lds, q.in[1], q.in[2]);
+}
+
+// log_n = 0, where the transforms are the identity: out = (a b - c) s, s = (g - 1)^-1
+__global__ void __launch_bounds__(256) k_ntt_quotient_point(const uint64_t* a, const uint64_t* b, const uint64_t* c,
+                                                            uint64_t* out, const uint64_t* s, size_t count) {
+    Fr z;
+    fr_load(z, s);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
+        Fr x, y;
+        fr_load(x, a + 4 * i);
+        fr_load(y, b + 4 * i);
+        fr_mul(x, x, y);
+        fr_load(y, c + 4 * i);
+        fr_sub(x, x, y);
+        fr_mul(x, x, z);
+        fr_store(out + 4 * i, x);
     }
 }
 
@@ -260,14 +328,24 @@ PA_DEV void ntt_from_u32(Fr& r, uint32_t v) {
     fr_from_repr(r, c);
 }
 
-// kind 0: out[i] = w_n^(+-(i << shift)); kind 1: out[i] = g^(+-(i << shift)), times n^-1 if `scaled`;
-// kind 2: out[0] = n^-1
+// 1 / Z on the coset, Z = X^n - 1: (g^n - 1)^-1
+PA_DEV void ntt_zinv(Fr& r, uint32_t log_n) {
+    Fr g, one;
+    ntt_from_u32(g, 7);
+    ntt_pow_u32(r, g, 1u << log_n);
+    fr_one(one);
+    fr_sub(r, r, one);   // g has order r - 1 > 2^28: never zero
+    fr_inv(r, r);
+}
+
+// kind 0: out[i] = w_n^(+-(i << shift)); kind 1: out[i] = g^(+-(i << shift)), times n^-1 if `scaled`, and
+// times 1 / Z as well if `scaled` is 2; kind 2: out[0] = n^-1; kind 3: out[0] = n^-1 / Z
 __global__ void __launch_bounds__(64) k_ntt_table(uint64_t* out, uint32_t count, uint32_t kind, uint32_t log_n,
                                                   uint32_t shift, uint32_t inverse, uint32_t scaled) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     Fr r, ninv;
-    if (kind != 0 && (kind == 2 || scaled)) {
+    if (kind != 0 && (kind >= 2 || scaled)) {
         Fr n;
         ntt_from_u32(n, 1u << log_n);
         fr_inv(ninv, n);
@@ -286,8 +364,16 @@ __global__ void __launch_bounds__(64) k_ntt_table(uint64_t* out, uint32_t count,
         if (inverse) fr_inv(g, g);
         ntt_pow_u32(r, g, i << shift);
         if (scaled) fr_mul(r, r, ninv);
-    } else {
+        if (scaled == 2) {
+            Fr z;
+            ntt_zinv(z, log_n);
+            fr_mul(r, r, z);
+        }
+    } else if (kind == 2) {
         r = ninv;
+    } else {
+        ntt_zinv(r, log_n);
+        fr_mul(r, r, ninv);
     }
     fr_store(out + 4 * (size_t)i, r);
 }
@@ -355,6 +441,9 @@ NttLayout ntt_layout(unsigned log_n, unsigned tile_log) {
         l.ghi[d] = at, at += l.hi_rows;
     }
     l.ninv = at++;
+    // the quotient's constants, after every row the transforms use
+    l.qscale = at++;
+    for (int i = 0; i < 2; i++) l.qglo[i] = at, at += l.lo_rows;
     l.rows = at;
     return l;
 }
@@ -381,11 +470,16 @@ hipError_t launch_ntt_build(const NttLayout& l, uint64_t* tables, hipStream_t st
     };
     const unsigned tmax = l.log_n < l.tile_log ? l.log_n : l.tile_log;
     if (ntt_group_log(l) > kNttGroupLog) {   // more than the 64 KiB a kernel may use unasked
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 32 << ntt_group_log(l));
-        if (e != hipSuccess) return e;
+        const void* kernels[3] = {reinterpret_cast<const void*>(k_ntt_pass),
+                                  reinterpret_cast<const void*>(k_ntt_pass3<false>),
+                                  reinterpret_cast<const void*>(k_ntt_pass3<true>)};
+        for (const void* k : kernels) {
+            const hipError_t e =
+                hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 32 << ntt_group_log(l));
+            if (e != hipSuccess) return e;
+        }
     }
-    Job jobs[11];
+    Job jobs[14];
     int nj = 0;
     for (uint32_t d = 0; d < 2; d++) {
         jobs[nj++] = {l.tile[d], l.tile_rows, 0, l.log_n - tmax, d, 0};
@@ -395,6 +489,9 @@ hipError_t launch_ntt_build(const NttLayout& l, uint64_t* tables, hipStream_t st
         jobs[nj++] = {l.ghi[d], l.hi_rows, 1, l.split_log, d, 0};
     }
     jobs[nj++] = {l.ninv, 1, 2, 0, 0, 0};
+    jobs[nj++] = {l.qscale, 1, 3, 0, 0, 0};
+    jobs[nj++] = {l.qglo[0], l.lo_rows, 1, 0, 0, 2};   // g^i n^-1 / Z
+    jobs[nj++] = {l.qglo[1], l.lo_rows, 1, 0, 0, 1};   // g^i n^-1
     for (int j = 0; j < nj; j++) {
         if (!jobs[j].count) continue;
         hipLaunchKernelGGL(k_ntt_table, dim3((unsigned)((jobs[j].count + 63) / 64)), dim3(64), 0, stream,
@@ -435,6 +532,82 @@ hipError_t launch_ntt(const NttLayout& l, const uint64_t* tables, int mode, cons
         hipLaunchKernelGGL(k_ntt_pass, dim3((unsigned)plan.tiles[q]), dim3(kNttThreads), lds, stream, p);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// ---- the quotient h = (A B - C) / Z of a proof, coefficients from evaluations ----
+size_t ntt_quotient_workspace_bytes(const NttLayout& l, size_t batch) {
+    if (l.log_n == 0) return 0;
+    return (l.passes > 1 ? 6 : 3) * (batch << l.log_n) * 32;   // three coset evaluations, and a pass workspace for three arrays
+}
+
+bool ntt_quotient_fits(const NttLayout& l, size_t batch) {
+    if (batch > (((size_t)1 << 40) / 3) || !ntt_batch_fits(l, 3 * batch)) return false;
+    NttPlan plan;
+    ntt_plan(l, batch, plan);
+    for (unsigned q = 0; q < plan.passes; q++)
+        if (3 * plan.tiles[q] > 0xffffffull) return false;   // each array has a batch tail of its own
+    return true;
+}
+
+hipError_t launch_ntt_quotient(const NttLayout& l, const uint64_t* tables, const uint64_t* a, const uint64_t* b,
+                               const uint64_t* c, uint64_t* out, size_t batch, void* workspace, hipStream_t stream) {
+    if (batch == 0) return hipSuccess;
+    if (!ntt_quotient_fits(l, batch)) return hipErrorInvalidValue;
+    const uint64_t* ninv = tables + 4 * l.ninv;
+    const uint64_t* qscale = tables + 4 * l.qscale;
+    if (l.log_n == 0) {
+        size_t blocks = (batch + 255) / 256;
+        if (blocks > stream_cfg().max_blocks) blocks = stream_cfg().max_blocks;
+        hipLaunchKernelGGL(k_ntt_quotient_point, dim3((unsigned)blocks), dim3(256), 0, stream, a, b, c, out, qscale,
+                           batch);
+        return hipGetLastError();
+    }
+    NttPlan plan;
+    ntt_plan(l, batch, plan);
+    const size_t words = (batch << l.log_n) * 4;   // u64 words of one array
+    uint64_t* ev = static_cast<uint64_t*>(workspace);
+    uint64_t* pw = ev + 3 * words;   // touched only by domains of several passes
+    const uint64_t* src[3] = {a, b, c};
+    // stage 0: the inverse transforms of a, b and c, left unscaled; stage 1: their coset forward transforms in
+    // place, whose coset factors g^i carry the n^-1 stage 0 left out and, for a and c, 1 / Z as well
+    // ((A B - C) / Z = (A / Z) B - C / Z); stage 2: the coset inverse transform of that product minus C / Z
+    for (int stage = 0; stage < 3; stage++) {
+        const int d = stage == 1 ? 0 : 1;
+        for (unsigned q = 0; q < plan.passes; q++) {
+            const bool first = q == 0, last = q + 1 == plan.passes;
+            NttPass3 k{};
+            NttPass& p = k.p;
+            p = plan.pass[q];
+            p.tw = tables + 4 * l.tile[d];
+            p.lo = tables + 4 * l.lo[d];
+            p.hi = tables + 4 * l.hi[d];
+            p.glo = tables + 4 * l.glo[d];
+            p.ghi = tables + 4 * l.ghi[d];
+            p.pre_coset = first && stage == 1;
+            p.post_coset = last && stage == 2;
+            p.scale = ninv;   // not read: no stage has a post_scale
+            k.tiles = (uint32_t)plan.tiles[q];
+            for (int i = 0; i < 3; i++) {
+                k.in[i] = first ? (stage == 0 ? src[i] : ev + i * words) : pw + i * words;
+                k.out[i] = last ? ev + i * words : pw + i * words;
+                k.glo[i] = stage == 1 ? tables + 4 * l.qglo[i == 1] : p.glo;
+            }
+            const size_t lds = (size_t)32 << (p.t + p.cbits);
+            if (stage < 2) {
+                hipLaunchKernelGGL(k_ntt_pass3<false>, dim3(3 * k.tiles), dim3(kNttThreads), lds, stream, k);
+            } else if (first) {
+                k.out[0] = last ? out : pw;
+                hipLaunchKernelGGL(k_ntt_pass3<true>, dim3(k.tiles), dim3(kNttThreads), lds, stream, k);
+            } else {
+                p.in = pw;
+                p.out = last ? out : pw;
+                hipLaunchKernelGGL(k_ntt_pass, dim3(k.tiles), dim3(kNttThreads), lds, stream, p);
+            }
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
     }
     return hipSuccess;
 }

@@ -226,6 +226,9 @@ struct NttLayout {
     unsigned log_n, tile_log, split_log, passes;
     size_t tile_rows, lo_rows, hi_rows;      // table lengths
     size_t tile[2], lo[2], hi[2], glo[2], ghi[2], ninv;   // [0] forward, [1] inverse
+    // the quotient's constants, after the transforms' own rows: n^-1 / Z (Z = g^n - 1; what log_n = 0 uses), and
+    // the forward low coset table times [0] n^-1 / Z, [1] n^-1
+    size_t qscale, qglo[2];
     size_t rows;                             // total
 };
 NttLayout ntt_layout(unsigned log_n, unsigned tile_log);
@@ -241,6 +244,17 @@ hipError_t launch_ntt_build(const NttLayout& l, uint64_t* tables, hipStream_t st
 // (in place there) -> out, so `in` is only read
 hipError_t launch_ntt(const NttLayout& l, const uint64_t* tables, int mode, const uint64_t* in, uint64_t* out,
                       size_t batch, void* workspace, hipStream_t stream);
+// The quotient of a proof: out_j = coset_inverse((coset_forward(inverse(a_j)) * coset_forward(inverse(b_j))
+// - coset_forward(inverse(c_j))) / (g^n - 1)), a, b and c three arrays of `batch` polynomials.  3 x passes
+// launches: each pass of the first two transforms runs over the three arrays in one grid, the pointwise step
+// is the load of the last transform's first pass, and the inverse transforms' n^-1 and 1 / (g^n - 1) ride on
+// the coset factors of the forward transforms (a's and c's).  a, b, c are only read (out may be any of them, they may be one another); the workspace holds
+// the three coset evaluations and, for several passes, a pass workspace for three arrays.
+size_t ntt_quotient_workspace_bytes(const NttLayout& l, size_t batch);
+// false if a pass over the three arrays would need more workgroups than a grid holds
+bool ntt_quotient_fits(const NttLayout& l, size_t batch);
+hipError_t launch_ntt_quotient(const NttLayout& l, const uint64_t* tables, const uint64_t* a, const uint64_t* b,
+                               const uint64_t* c, uint64_t* out, size_t batch, void* workspace, hipStream_t stream);
 
 // ---- bit-exact Wnaf (kernels_wnaf_exact.hip) ----
 constexpr int kWxMaxWindow = 20;         // fixed base: 2^19 table entries, int32 digits

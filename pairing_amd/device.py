@@ -335,6 +335,34 @@ def fr_ntt(domain, a, out, mode, workspace=None, stream=None):
     call("pa_fr_ntt_device", h, m, *args, batch, ws, need * 8, _stream_ptr(stream))
 
 
+def fr_ntt_quotient_workspace_words(domain, batch):
+    """int64 words of `workspace` for fr_ntt_quotient over `batch` polynomial triples (0 for log_n = 0)."""
+    return (domain.quotient_workspace_bytes(batch) + 7) // 8
+
+
+def fr_ntt_quotient(domain, a, b, c, out, workspace=None, stream=None):
+    """The quotient of a proof: from the evaluations a, b, c of each of batch polynomial
+    triples ((rows, 4) int64 Montgomery Fr, laid out as fr_ntt's) the coefficients of
+    h = (A B - C) / (X^n - 1) into the first batch * n rows of `out`, which may be a, b or
+    c itself; the other inputs are only read and rows of out past the batch are left
+    alone.  workspace: an int64 buffer of fr_ntt_quotient_workspace_words(domain, batch),
+    not needed where that is 0.  Nothing is allocated or read back; `out` is what
+    multiexp_prepared_batch(..., montgomery=True) takes."""
+    if not isinstance(domain, FrNttDomain):
+        raise ValueError("domain must come from fr_ntt_domain")
+    domain.handle()   # a closed object is rejected first
+    h, batch = domain.check_rows(a.shape[0])
+    _rows(b, a.shape[0], "b")
+    _rows(c, a.shape[0], "c")
+    _rows(out, a.shape[0], "out")
+    need = fr_ntt_quotient_workspace_words(domain, batch)
+    if need and workspace is None:
+        raise ValueError("workspace must be a contiguous int64 CUDA tensor of >= %d words" % need)
+    ws = _words(workspace, need, "workspace") if need else ctypes.c_void_p(0)
+    args = (_dptr(a, 4, "a"), _dptr(b, 4, "b"), _dptr(c, 4, "c"), _dptr(out, 4, "out"))
+    call("pa_fr_ntt_quotient_device", h, *args, batch, ws, need * 8, _stream_ptr(stream))
+
+
 def multiexp_workspace(group, n, device):
     """A device workspace sized for pa_g{group}_multiexp_device over n terms."""
     nbytes = int(_lib.pa_multiexp_workspace_bytes(int(group), int(n)))
