@@ -577,6 +577,116 @@ int pa_fr_ntt_quotient(const pa_fr_ntt_domain *d, const pa_fr *a, const pa_fr *b
 int pa_fr_ntt_quotient_device(const pa_fr_ntt_domain *d, const pa_fr *a, const pa_fr *b, const pa_fr *c, pa_fr *out,
                               size_t batch, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- R1CS matrices on the device: A w, B w, C w over the domain ----
+ * The three arrays the quotient takes are the products of a constraint
+ * system's matrices with the witness.  pa_r1cs holds the three matrices on one
+ * device; an evaluation multiplies them with k witnesses in one call.
+ *   witness: k vectors of n_cols Montgomery pa_fr rows, end to end;
+ *   a, b, c: k polynomials of n = 2^log_n rows each, end to end (the layout
+ *            of pa_fr_ntt and pa_fr_ntt_quotient); for witness j and i < n_rows
+ *            a[j n + i] = sum_t val[t] w_j[col[t]] over row i of A, likewise b
+ *            and c; rows n_rows .. n - 1 are written as zero.
+ * Every value is canonical, so the results are bit-exact whatever the order of
+ * summation.  A column may occur more than once in a row (the terms add); empty
+ * rows, an empty matrix, n_rows = 0, k = 0 (writes nothing) and log_n = 0 are
+ * valid.  A witness row that is not below r is undefined.
+ *
+ * Creation copies the matrices (host CSR) into a device image and waits for
+ * the copy; the host arrays may be released afterwards.  It cuts every row into
+ * chunks of at most pa_r1cs_chunk_len() terms: one lane sums one chunk, a row of
+ * one chunk stores its sum, a row of several gets its partial sums added by a
+ * second, small launch (no atomics), so a row of thousands of terms among rows
+ * of one to three does not set the kernel's time.  Errors at creation
+ * (PA_ERR_INVALID_ARGUMENT, nothing allocated): row_ptr[0] != 0 or decreasing,
+ * a column >= n_cols, a value >= r, nnz >= 2^32 in one matrix, n_rows >
+ * 2^PA_NTT_MAX_LOG_N.  The object belongs to the device that was current at
+ * creation, may be used from any host thread and lives until pa_r1cs_free (NULL
+ * is a no-op); work that reads it must have completed before it is freed.
+ *
+ * Errors at evaluation (PA_ERR_INVALID_ARGUMENT, before any launch): 2^log_n <
+ * n_rows, log_n > PA_NTT_MAX_LOG_N, a workspace smaller than
+ * pa_r1cs_eval_workspace_bytes(r, k) (k times 32 bytes per chunk of the rows of
+ * several chunks; 0 if there are none, then workspace may be NULL), a stream on
+ * another device than the object's.  a, b, c, the witness and the workspace
+ * must not overlap.  The device entry allocates nothing, does not synchronize
+ * and reads nothing back. */
+typedef struct pa_r1cs pa_r1cs;
+/* host CSR: row_ptr[n_rows + 1] (row_ptr[0] = 0, non-decreasing), col[nnz] < n_cols, val[nnz] Montgomery pa_fr < r */
+typedef struct { const uint64_t *row_ptr; const uint32_t *col; const pa_fr *val; } pa_fr_csr;
+int pa_r1cs_create(const pa_fr_csr *a, const pa_fr_csr *b, const pa_fr_csr *c, size_t n_rows, size_t n_cols,
+                   pa_r1cs **out);
+void pa_r1cs_free(pa_r1cs *r);
+size_t pa_r1cs_rows(const pa_r1cs *r);
+size_t pa_r1cs_cols(const pa_r1cs *r);
+size_t pa_r1cs_bytes(const pa_r1cs *r);   /* device memory it holds */
+size_t pa_r1cs_chunk_len(void);
+size_t pa_r1cs_eval_workspace_bytes(const pa_r1cs *r, size_t k);
+int pa_r1cs_eval_device(const pa_r1cs *r, const pa_fr *dev_witness, size_t k, unsigned log_n, pa_fr *a, pa_fr *b,
+                        pa_fr *c, void *workspace, size_t workspace_bytes, void *stream);
+int pa_r1cs_eval(const pa_r1cs *r, const pa_fr *host_witness, size_t k, unsigned log_n, pa_fr *a, pa_fr *b,
+                 pa_fr *c);   /* host memory */
+
+/* ---- Groth16 prover: witness in, proof out, k proofs per call ----
+ * The proving key as one object on one device (the current one at creation),
+ * built on pa_g{1,2}_msm_bases_prepare.  n_public counts the constant one:
+ * variables [0, n_public) have no L entry.  The L query is stored with n_public
+ * points at infinity in front and the H query with points at infinity up to
+ * 2^log_n, so the multiexps read the witness at stride n_vars and the quotient
+ * at stride n as they lie (a consequence: the top row of h, nonzero only for an
+ * unsatisfied witness, meets infinity when h_len < n and drops out, as it does
+ * in bellman, which gives h_len = n - 1).  Creation fails with
+ * PA_ERR_INVALID_ARGUMENT for n_public > n_vars, h_len > 2^log_n or log_n >
+ * PA_NTT_MAX_LOG_N.  pa_groth16_pk_in_subgroup is 1 if all five query sets
+ * passed their membership test (the multiexps then take the GLV path); the
+ * proof is the same either way.  alpha, beta and delta are not tested; for
+ * delta the key also holds 2^i delta, i < 255, in both groups (109 KiB), which
+ * the assembly sums instead of doubling.
+ *
+ * pa_groth16_prove*: for proof j with witness w (n_vars rows), z = n_public, h
+ * the n rows of pa_fr_ntt_quotient over pa_r1cs_eval of w, and r, s its
+ * blinding scalars (one Montgomery row each per proof, supplied by the caller)
+ *   A  = alpha_g1 + sum_i w_i a_query[i]    + r delta_g1
+ *   B  = beta_g2  + sum_i w_i b_g2_query[i] + s delta_g2
+ *   B1 = beta_g1  + sum_i w_i b_g1_query[i] + s delta_g1
+ *   C  = sum_{i >= z} w_i l_query[i - z] + sum_i h_i h_query[i] + s A + r B1 - (r s) delta_g1
+ * (bellman's create_proof), written as the affine records that
+ * pa_g{1,2}_into_affine_batch write for those points, infinity included:
+ * affine coordinates are canonical, so a proof is bit-exact.  The device entry
+ * runs pa_r1cs_eval_device, pa_fr_ntt_quotient_device, four G1 and one G2
+ * pa_g*_multiexp_prepared_batch_device with PA_MSM_SCALARS_MONTGOMERY and one
+ * assembly kernel on `stream`: it allocates nothing, forks no stream and does
+ * not synchronize.  The workspace holds a, b, c, the five sums and one region
+ * that the steps use one after the other; ..._workspace_bytes returns 0 when
+ * the batch is over a multiexp's 32-bit item limit or the quotient's grid
+ * limit, and the entries then return PA_ERR_INVALID_ARGUMENT: split the batch.
+ * Errors, all PA_ERR_INVALID_ARGUMENT before anything runs: the domain's log_n
+ * differs from the key's, pa_r1cs_cols(r1cs) != n_vars, pa_r1cs_rows(r1cs) >
+ * 2^log_n, objects or stream on different devices, a batch over the limit, a
+ * workspace that is too small.  k = 0 writes nothing.  A witness, r or s row
+ * that is not below r is undefined. */
+typedef struct {
+    pa_g1_affine alpha_g1, beta_g1, delta_g1;
+    pa_g2_affine beta_g2, delta_g2;
+    size_t n_vars, n_public;
+    const pa_g1_affine *a_query, *b_g1_query;   /* n_vars each; infinity where a variable does not occur */
+    const pa_g2_affine *b_g2_query;             /* n_vars */
+    const pa_g1_affine *l_query;                /* n_vars - n_public */
+    const pa_g1_affine *h_query;                /* h_len <= 2^log_n */
+    size_t h_len;
+} pa_groth16_key;   /* host memory */
+typedef struct pa_groth16_pk pa_groth16_pk;
+typedef struct { pa_g1_affine a; pa_g2_affine b; pa_g1_affine c; } pa_groth16_proof;   /* 51 u64 */
+int pa_groth16_pk_create(const pa_groth16_key *key, unsigned log_n, pa_groth16_pk **out);
+void pa_groth16_pk_free(pa_groth16_pk *pk);   /* NULL is a no-op */
+int pa_groth16_pk_in_subgroup(const pa_groth16_pk *pk);
+size_t pa_groth16_prove_workspace_bytes(const pa_groth16_pk *pk, const pa_r1cs *r1cs, size_t k);
+int pa_groth16_prove_device(const pa_groth16_pk *pk, const pa_r1cs *r1cs, const pa_fr_ntt_domain *d,
+                            const pa_fr *dev_witness, const pa_fr *dev_r, const pa_fr *dev_s, size_t k,
+                            pa_groth16_proof *dev_proofs, void *workspace, size_t workspace_bytes, void *stream);
+int pa_groth16_prove(const pa_groth16_pk *pk, const pa_r1cs *r1cs, const pa_fr_ntt_domain *d,
+                     const pa_fr *host_witness, const pa_fr *host_r, const pa_fr *host_s, size_t k,
+                     pa_groth16_proof *proofs);   /* host memory */
+
 /* ---- device-resident variants (pointers are device memory) ---- */
 int pa_g1_decode_batch_device(const uint8_t *enc, size_t n, int compressed, int checked, pa_g1_affine *out,
                               uint8_t *status, void *stream);

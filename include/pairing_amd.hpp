@@ -721,6 +721,106 @@ private:
     pa_fr_ntt_domain* h_ = nullptr;
 };
 
+// The matrices A, B, C of a constraint system on the device (pa_r1cs), from
+// host CSR triples.  Move-only; the destructor frees the device memory.
+class R1cs {
+public:
+    struct Csr {   // row_ptr: n_rows + 1 entries from 0, non-decreasing; val: Montgomery rows below r
+        std::vector<uint64_t> row_ptr;
+        std::vector<uint32_t> col;
+        std::vector<pa_fr> val;
+    };
+    struct Evals {   // k polynomials of 2^log_n rows each, end to end
+        std::vector<pa_fr> a, b, c;
+    };
+    R1cs(const Csr& a, const Csr& b, const Csr& c, size_t n_rows, size_t n_cols) {
+        const Csr* ms[3] = {&a, &b, &c};
+        pa_fr_csr raw[3];
+        for (int i = 0; i < 3; i++) {
+            if (ms[i]->row_ptr.size() != n_rows + 1 || ms[i]->col.size() != ms[i]->val.size() ||
+                ms[i]->row_ptr.back() != ms[i]->col.size())
+                throw std::invalid_argument("R1cs: row_ptr, col and val do not describe n_rows rows");
+            raw[i] = {ms[i]->row_ptr.data(), ms[i]->col.data(), ms[i]->val.data()};
+        }
+        check(pa_r1cs_create(&raw[0], &raw[1], &raw[2], n_rows, n_cols, &h_), "R1cs");
+    }
+    R1cs(const R1cs&) = delete;
+    R1cs& operator=(const R1cs&) = delete;
+    R1cs(R1cs&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    R1cs& operator=(R1cs&& o) noexcept {
+        if (this != &o) {
+            pa_r1cs_free(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~R1cs() { pa_r1cs_free(h_); }
+
+    size_t rows() const { return pa_r1cs_rows(h_); }
+    size_t cols() const { return pa_r1cs_cols(h_); }
+    const pa_r1cs* get() const { return h_; }
+    // A w, B w, C w over the domain of 2^log_n points for the k witnesses of `witness` (k cols() rows)
+    Evals eval(const std::vector<pa_fr>& witness, size_t k, unsigned log_n) const {
+        if (witness.size() != k * cols()) throw std::invalid_argument("R1cs::eval: witness is not k vectors of cols()");
+        if (log_n > PA_NTT_MAX_LOG_N) throw std::invalid_argument("R1cs::eval: log_n over PA_NTT_MAX_LOG_N");
+        Evals e;
+        e.a.resize(k << log_n);
+        e.b.resize(k << log_n);
+        e.c.resize(k << log_n);
+        check(pa_r1cs_eval(h_, witness.data(), k, log_n, e.a.data(), e.b.data(), e.c.data()), "R1cs::eval");
+        return e;
+    }
+
+private:
+    pa_r1cs* h_ = nullptr;
+};
+
+// A Groth16 prover: the proving key prepared on the device (pa_groth16_pk), the
+// constraint system and the evaluation domain of 2^log_n points.  prove() runs
+// witness -> proof for k proofs in one call.  The prover keeps a pointer to the
+// R1cs, which must outlive it.  Move-only.
+class Groth16Prover {
+public:
+    Groth16Prover(const pa_groth16_key& key, const R1cs& r1cs, unsigned log_n) : r1cs_(&r1cs), domain_(log_n) {
+        check(pa_groth16_pk_create(&key, log_n, &pk_), "Groth16Prover");
+    }
+    Groth16Prover(const Groth16Prover&) = delete;
+    Groth16Prover& operator=(const Groth16Prover&) = delete;
+    Groth16Prover(Groth16Prover&& o) noexcept : pk_(o.pk_), r1cs_(o.r1cs_), domain_(std::move(o.domain_)) {
+        o.pk_ = nullptr;
+    }
+    Groth16Prover& operator=(Groth16Prover&& o) noexcept {
+        if (this != &o) {
+            pa_groth16_pk_free(pk_);
+            pk_ = o.pk_;
+            o.pk_ = nullptr;
+            r1cs_ = o.r1cs_;
+            domain_ = std::move(o.domain_);
+        }
+        return *this;
+    }
+    ~Groth16Prover() { pa_groth16_pk_free(pk_); }
+
+    bool in_subgroup() const { return pa_groth16_pk_in_subgroup(pk_) != 0; }
+    const pa_groth16_pk* get() const { return pk_; }
+    // k proofs: witness k n_vars rows, r and s k rows (Montgomery, below r)
+    std::vector<pa_groth16_proof> prove(const std::vector<pa_fr>& witness, const std::vector<pa_fr>& r,
+                                        const std::vector<pa_fr>& s, size_t k) const {
+        if (r.size() != k || s.size() != k || witness.size() != k * r1cs_->cols())
+            throw std::invalid_argument("Groth16Prover::prove: witness, r and s are not k proofs' rows");
+        std::vector<pa_groth16_proof> out(k);
+        check(pa_groth16_prove(pk_, r1cs_->get(), domain_.get(), witness.data(), r.data(), s.data(), k, out.data()),
+              "Groth16Prover::prove");
+        return out;
+    }
+
+private:
+    pa_groth16_pk* pk_ = nullptr;
+    const R1cs* r1cs_;
+    FrNttDomain domain_;
+};
+
 using G1Uncompressed = Encoded<G1Affine, 1, false>;
 using G1Compressed = Encoded<G1Affine, 1, true>;
 using G2Uncompressed = Encoded<G2Affine, 2, false>;

@@ -17,6 +17,7 @@ Device-resident entry points for torch tensors live in `pairing_amd.device`.
 import numpy as np
 
 from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, NTT_MAX_LOG_N, FrNttDomain, G1MsmBases, G2MsmBases,
+                      FrCsr, Groth16Key, Groth16Pk, R1cs, R1CS_CHUNK_LEN, W_PROOF,
                       PairingError, _lib, as_rows, batch_shape, call, csr_offsets, device_count, msm_bases, msm_scalars, ntt_mode, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
 
 __all__ = [
@@ -36,6 +37,7 @@ __all__ = [
     "G1MsmBases", "g1_msm_prepare", "g1_multiexp_prepared", "g1_multiexp_prepared_batch",
     "G2MsmBases", "g2_msm_prepare", "g2_multiexp_prepared", "g2_multiexp_prepared_batch",
     "FrNttDomain", "fr_ntt_domain", "fr_ntt", "fr_ntt_quotient",
+    "R1cs", "r1cs", "r1cs_eval", "R1CS_CHUNK_LEN", "Groth16Pk", "groth16_pk", "groth16_prove",
     "g1_eq", "g2_eq", "g1_double", "g2_double", "g1_add", "g2_add", "g1_add_mixed", "g2_add_mixed", "g1_negate", "g2_negate",
     "g1_sub", "g2_sub", "g1_into_affine", "g2_into_affine", "g1_into_projective", "g2_into_projective",
     "g2_batch_normalization", "g2_wnaf_fixed_base",
@@ -733,6 +735,126 @@ def fr_ntt_quotient(domain, a, b, c):
     out = np.zeros_like(a)
     if batch:
         call("pa_fr_ntt_quotient", h, ptr(a), ptr(b), ptr(c), ptr(out), batch)
+    return out
+
+
+# ---- R1CS matrices on the device and the Groth16 prover ----
+def _csr(m, n_rows, n_cols, name):
+    """(FrCsr, the arrays it points into) of one (row_ptr, col, val) triple, checked as pa_r1cs_create checks it"""
+    import ctypes
+    try:
+        row_ptr, col, val = m
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a (row_ptr, col, val) triple" % name) from None
+    rp = np.asarray(row_ptr)
+    co = np.asarray(col)
+    if rp.ndim != 1 or rp.shape[0] != n_rows + 1 or (rp.size and rp.dtype.kind not in "iu"):
+        raise ValueError("%s: row_ptr must be a 1-d integer array of n_rows + 1 = %d entries" % (name, n_rows + 1))
+    if rp.dtype.kind == "i" and (rp < 0).any():
+        raise ValueError("%s: row_ptr must not be negative" % name)
+    rp = np.ascontiguousarray(rp, dtype=np.uint64)
+    if int(rp[0]) != 0 or (rp[1:] < rp[:-1]).any():
+        raise ValueError("%s: row_ptr must start at 0 and be non-decreasing" % name)
+    nnz = int(rp[-1])
+    if nnz >= 1 << 32:
+        raise ValueError("%s: nnz must be below 2^32" % name)
+    if co.ndim != 1 or co.shape[0] != nnz or (nnz and co.dtype.kind not in "iu"):
+        raise ValueError("%s: col must be a 1-d integer array of nnz = %d entries" % (name, nnz))
+    if nnz and (int(co.min()) < 0 or int(co.max()) >= n_cols):
+        raise ValueError("%s: a column index is not below n_cols = %d" % (name, n_cols))
+    co = np.ascontiguousarray(co, dtype=np.uint32)
+    va = as_rows(val, W_FR, name + " val") if nnz else np.zeros((0, W_FR), np.uint64)
+    if va.shape[0] != nnz:
+        raise ValueError("%s: val must have nnz = %d rows, got %d" % (name, nnz, va.shape[0]))
+    keep = (rp, co, va)
+    return FrCsr(ctypes.c_void_p(rp.ctypes.data), ctypes.c_void_p(co.ctypes.data), ctypes.c_void_p(va.ctypes.data)), keep
+
+
+def r1cs(a, b, c, n_rows, n_cols):
+    """The matrices of a constraint system on the current device: a, b, c are CSR
+    triples (row_ptr (n_rows + 1,), col (nnz,), val (nnz, 4) Montgomery Fr below r).
+    Returns an R1cs (rows, cols, bytes, close()).  A value >= r is refused by the
+    library (PairingError); everything else is a ValueError here."""
+    import ctypes
+    n_rows, n_cols = int(n_rows), int(n_cols)
+    if n_rows < 0 or n_cols < 0 or n_rows > 1 << NTT_MAX_LOG_N:
+        raise ValueError("n_rows must be 0..2^%d and n_cols >= 0" % NTT_MAX_LOG_N)
+    ms = [_csr(m, n_rows, n_cols, name) for m, name in ((a, "a"), (b, "b"), (c, "c"))]
+    h = ctypes.c_void_p(0)
+    call("pa_r1cs_create", *(ctypes.byref(m[0]) for m in ms), n_rows, n_cols, ctypes.byref(h))
+    return R1cs._adopt(h)
+
+
+def r1cs_eval(system, witness, log_n, count=None):
+    """(a, b, c), each (k * 2^log_n, 4): the products of the system's matrices with k
+    witnesses ((k * cols, 4) Montgomery Fr rows end to end; count=k is needed only
+    for a system of no columns), laid out as fr_ntt_quotient takes them; rows from
+    the system's rows up to 2^log_n are zero."""
+    if not isinstance(system, R1cs):
+        raise ValueError("system must come from r1cs()")
+    system.handle()   # a closed object is rejected first
+    w = as_rows(witness, W_FR, "witness") if len(witness) else np.zeros((0, W_FR), np.uint64)
+    h, k, log_n = system.check_eval(w.shape[0], count, log_n)
+    outs = tuple(np.zeros((k << log_n, W_FR), np.uint64) for _ in range(3))
+    if k:
+        call("pa_r1cs_eval", h, ptr(w), k, log_n, *(ptr(o) for o in outs))
+    return outs
+
+
+def groth16_pk(alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2, a_query, b_g1_query, b_g2_query, l_query, h_query,
+               n_public, log_n):
+    """A proving key on the current device (pa_groth16_pk_create): alpha_g1, beta_g1,
+    delta_g1 (1, 13) and beta_g2, delta_g2 (1, 25) affine records; a_query, b_g1_query
+    (n_vars, 13), b_g2_query (n_vars, 25), l_query (n_vars - n_public, 13) and h_query
+    (h_len <= 2^log_n, 13).  n_public counts the constant one.  Returns a Groth16Pk."""
+    import ctypes
+    def rows(x, width, name):
+        return as_rows(x, width, name) if len(x) else np.zeros((0, width), np.uint64)
+    singles = [rows(x, w, name) for x, w, name in ((alpha_g1, W_G1A, "alpha_g1"), (beta_g1, W_G1A, "beta_g1"),
+                                                   (delta_g1, W_G1A, "delta_g1"), (beta_g2, W_G2A, "beta_g2"),
+                                                   (delta_g2, W_G2A, "delta_g2"))]
+    for x, name in zip(singles, ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2")):
+        if x.shape[0] != 1:
+            raise ValueError("%s must be one affine record, got %d" % (name, x.shape[0]))
+    aq, b1q, lq, hq = (rows(x, W_G1A, name) for x, name in ((a_query, "a_query"), (b_g1_query, "b_g1_query"),
+                                                             (l_query, "l_query"), (h_query, "h_query")))
+    b2q = rows(b_g2_query, W_G2A, "b_g2_query")
+    n_vars, n_public, log_n = aq.shape[0], int(n_public), int(log_n)
+    if log_n < 0 or log_n > NTT_MAX_LOG_N:
+        raise ValueError("log_n must be 0..%d, got %d" % (NTT_MAX_LOG_N, log_n))
+    if b1q.shape[0] != n_vars or b2q.shape[0] != n_vars:
+        raise ValueError("a_query, b_g1_query and b_g2_query must have n_vars rows each, got %d, %d and %d"
+                         % (n_vars, b1q.shape[0], b2q.shape[0]))
+    if n_public < 0 or n_public > n_vars or lq.shape[0] != n_vars - n_public:
+        raise ValueError("l_query must have n_vars - n_public = %d rows, got %d" % (n_vars - n_public, lq.shape[0]))
+    if hq.shape[0] > 1 << log_n:
+        raise ValueError("h_query has %d rows, the domain %d points" % (hq.shape[0], 1 << log_n))
+    key = Groth16Key()
+    for field, x in zip(("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2"), singles):
+        ctypes.memmove(getattr(key, field), x.ctypes.data, x.nbytes)
+    key.n_vars, key.n_public, key.h_len = n_vars, n_public, hq.shape[0]
+    for field, x in (("a_query", aq), ("b_g1_query", b1q), ("b_g2_query", b2q), ("l_query", lq), ("h_query", hq)):
+        setattr(key, field, x.ctypes.data)
+    h = ctypes.c_void_p(0)
+    call("pa_groth16_pk_create", ctypes.byref(key), log_n, ctypes.byref(h))
+    h = ctypes.c_void_p(h.value)
+    return Groth16Pk(h, log_n, n_vars, n_public, hq.shape[0], _lib.pa_groth16_pk_in_subgroup(h))
+
+
+def groth16_prove(pk, system, domain, witness, r, s):
+    """k Groth16 proofs in one call (pa_groth16_prove): witness (k * n_vars, 4), r and s
+    (k, 4) Montgomery Fr rows below r.  Returns (k, 51) uint64 rows, one
+    pa_groth16_proof each: the affine records A (words 0..12), B (13..37) and C
+    (38..50), bit for bit what into_affine of bellman's create_proof points gives."""
+    if not isinstance(pk, Groth16Pk):
+        raise ValueError("pk must come from groth16_pk")
+    pk.handle()   # a closed object is rejected first
+    w, r, s = (as_rows(x, W_FR, name) if len(x) else np.zeros((0, W_FR), np.uint64)
+               for x, name in ((witness, "witness"), (r, "r"), (s, "s")))
+    (h, hr, hd), k = pk.check_prove(system, domain, w.shape[0], r.shape[0], s.shape[0])
+    out = np.zeros((k, W_PROOF), np.uint64)
+    if k:
+        call("pa_groth16_prove", h, hr, hd, ptr(w), ptr(r), ptr(s), k, ptr(out))
     return out
 
 

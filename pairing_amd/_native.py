@@ -218,6 +218,18 @@ _SIGS.update({
     "pa_g2_wnaf_fixed_base_window": [_P, _P, _N, ctypes.c_int, _P],
     "pa_g2_wnaf_fixed_base_device": [_P, _P, _P, _N, _P, _P, _P],
     "pa_g2_wnaf_fixed_base_window_device": [_P, _P, _P, _N, ctypes.c_int, _P, _P, _P],
+    "pa_r1cs_create": [_P, _P, _P, _N, _N, ctypes.POINTER(_P)],
+    "pa_r1cs_eval_device": [_P, _P, _N, ctypes.c_uint, _P, _P, _P, _P, _N, _P],
+    "pa_r1cs_eval": [_P, _P, _N, ctypes.c_uint, _P, _P, _P],
+    "pa_r1cs_rows": [_P],                             # these four return size_t (below)
+    "pa_r1cs_cols": [_P],
+    "pa_r1cs_bytes": [_P],
+    "pa_r1cs_eval_workspace_bytes": [_P, _N],
+    "pa_groth16_pk_create": [_P, ctypes.c_uint, ctypes.POINTER(_P)],
+    "pa_groth16_pk_in_subgroup": [_P],
+    "pa_groth16_prove_workspace_bytes": [_P, _P, _N],   # returns size_t (below)
+    "pa_groth16_prove_device": [_P, _P, _P, _P, _P, _P, _N, _P, _P, _N, _P],
+    "pa_groth16_prove": [_P, _P, _P, _P, _P, _P, _N, _P],
 })
 for _name, _args in _SIGS.items():
     _fn = getattr(_lib, _name)
@@ -243,6 +255,13 @@ for _name in ("pa_fr_ntt_domain_log_n", "pa_fr_ntt_domain_passes", "pa_fr_ntt_do
 for _name in ("pa_fr_ntt_domain_bytes", "pa_fr_ntt_polys_per_workgroup", "pa_fr_ntt_workspace_bytes",
               "pa_fr_ntt_quotient_workspace_bytes"):
     getattr(_lib, _name).restype = ctypes.c_size_t
+for _name in ("pa_r1cs_rows", "pa_r1cs_cols", "pa_r1cs_bytes", "pa_r1cs_eval_workspace_bytes", "pa_r1cs_chunk_len",
+              "pa_groth16_prove_workspace_bytes"):
+    getattr(_lib, _name).restype = ctypes.c_size_t
+_lib.pa_r1cs_chunk_len.argtypes = []
+for _name in ("pa_r1cs_free", "pa_groth16_pk_free"):
+    getattr(_lib, _name).argtypes = [_P]
+    getattr(_lib, _name).restype = None
 
 
 def version():
@@ -508,3 +527,150 @@ class FrNttDomain:
             self.close()
         except Exception:   # interpreter shutdown: the library may be gone
             pass
+
+
+W_PROOF = W_G1A + W_G2A + W_G1A   # pa_groth16_proof: A (13), B (25), C (13) affine records
+R1CS_CHUNK_LEN = int(_lib.pa_r1cs_chunk_len())
+
+
+class _Handle:
+    """A device object of the C ABI behind an opaque pointer: close() frees it, is
+    idempotent and also runs when the object is collected; any use after close()
+    raises ValueError before a native call.  owns=False wraps a handle someone
+    else frees."""
+
+    WHAT = "object"
+    FREE = None   # name of the pa_*_free entry
+
+    def __init__(self, handle, owns=True):
+        self._handle = handle
+        self._owns = owns
+
+    @property
+    def closed(self):
+        return self._handle is None
+
+    def handle(self):
+        if self._handle is None:
+            raise ValueError("%s used after close()" % self.WHAT)
+        return self._handle
+
+    def close(self):
+        h, self._handle = self._handle, None
+        if h is not None and self._owns:
+            getattr(_lib, self.FREE)(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: the library may be gone
+            pass
+
+
+class R1cs(_Handle):
+    """A pa_r1cs handle: the matrices A, B, C of a constraint system on one device
+    (include/pairing_amd.h).  `rows`, `cols` and `bytes` (device memory held) are
+    read at creation."""
+
+    WHAT = "R1CS object"
+    FREE = "pa_r1cs_free"
+
+    def __init__(self, handle, rows, cols, nbytes=0, owns=True):
+        super().__init__(handle, owns)
+        self.rows, self.cols, self.bytes = int(rows), int(cols), int(nbytes)
+
+    @classmethod
+    def _adopt(cls, handle):
+        """take ownership of a handle pa_r1cs_create just returned"""
+        h = ctypes.c_void_p(handle.value)
+        return cls(h, _lib.pa_r1cs_rows(h), _lib.pa_r1cs_cols(h), _lib.pa_r1cs_bytes(h))
+
+    def check_eval(self, witness_rows, count, log_n):
+        """(handle, k, log_n) of an evaluation: `witness_rows` rows are k = count vectors of `cols` rows (count
+        None: as many as the rows hold), and 2^log_n covers the system's rows"""
+        h = self.handle()
+        log_n = int(log_n)
+        if log_n < 0 or log_n > NTT_MAX_LOG_N:
+            raise ValueError("log_n must be 0..%d, got %d" % (NTT_MAX_LOG_N, log_n))
+        if (1 << log_n) < self.rows:
+            raise ValueError("2^%d points do not hold the system's %d rows" % (log_n, self.rows))
+        if count is None:
+            if self.cols == 0:
+                raise ValueError("a system of no columns needs count=k")
+            count = witness_rows // self.cols
+        k = int(count)
+        if k < 0 or witness_rows != k * self.cols:
+            raise ValueError("%d witness rows are not %d vectors of %d" % (witness_rows, k, self.cols))
+        return h, k, log_n
+
+    def eval_workspace_bytes(self, k):
+        """pa_r1cs_eval_workspace_bytes(r, k): the partial sums of the rows of several chunks"""
+        return int(_lib.pa_r1cs_eval_workspace_bytes(self.handle(), int(k)))
+
+
+class Groth16Pk(_Handle):
+    """A pa_groth16_pk handle: a proving key's five query sets prepared for the
+    multiexps, and alpha, beta, delta, on one device.  `log_n`, `n_vars`,
+    `n_public`, `h_len` are what it was created with; `in_subgroup` says whether
+    all five sets passed their membership test."""
+
+    WHAT = "Groth16 key"
+    FREE = "pa_groth16_pk_free"
+
+    def __init__(self, handle, log_n, n_vars, n_public, h_len, in_subgroup=True, owns=True):
+        super().__init__(handle, owns)
+        self.log_n, self.n_vars, self.n_public, self.h_len = int(log_n), int(n_vars), int(n_public), int(h_len)
+        self.in_subgroup = bool(in_subgroup)
+
+    def check_prove(self, r1cs, domain, witness_rows, r_rows, s_rows):
+        """(handles, k) of a prove call after the checks that need no device"""
+        h = self.handle()
+        if not isinstance(r1cs, R1cs):
+            raise ValueError("r1cs must come from r1cs()")
+        if not isinstance(domain, FrNttDomain):
+            raise ValueError("domain must come from fr_ntt_domain")
+        hr, hd = r1cs.handle(), domain.handle()
+        if domain.log_n != self.log_n:
+            raise ValueError("the domain has log_n = %d, the key %d" % (domain.log_n, self.log_n))
+        if r1cs.cols != self.n_vars:
+            raise ValueError("the system has %d columns, the key %d variables" % (r1cs.cols, self.n_vars))
+        if r1cs.rows > (1 << self.log_n):
+            raise ValueError("the system's %d rows exceed the domain's %d points" % (r1cs.rows, 1 << self.log_n))
+        k = r_rows
+        if s_rows != k or witness_rows != k * self.n_vars:
+            raise ValueError("%d witness rows, %d r rows and %d s rows are not k proofs of %d variables"
+                             % (witness_rows, r_rows, s_rows, self.n_vars))
+        return (h, hr, hd), k
+
+    def prove_workspace_bytes(self, r1cs, k):
+        """pa_groth16_prove_workspace_bytes; a batch over the limit is a ValueError: split it"""
+        if not isinstance(r1cs, R1cs):
+            raise ValueError("r1cs must come from r1cs()")
+        k = int(k)
+        if k < 0:
+            raise ValueError("k must not be negative, got %d" % k)
+        n = int(_lib.pa_groth16_prove_workspace_bytes(self.handle(), r1cs.handle(), k))
+        if n == 0:
+            raise ValueError("a batch of %d proofs is over a multiexp's item limit, or the system does not fit the "
+                             "key: split it" % k)
+        return n
+
+
+class Groth16Key(ctypes.Structure):
+    """pa_groth16_key of the header"""
+    _fields_ = [("alpha_g1", ctypes.c_uint64 * W_G1A), ("beta_g1", ctypes.c_uint64 * W_G1A),
+                ("delta_g1", ctypes.c_uint64 * W_G1A), ("beta_g2", ctypes.c_uint64 * W_G2A),
+                ("delta_g2", ctypes.c_uint64 * W_G2A), ("n_vars", ctypes.c_size_t), ("n_public", ctypes.c_size_t),
+                ("a_query", _P), ("b_g1_query", _P), ("b_g2_query", _P), ("l_query", _P), ("h_query", _P),
+                ("h_len", ctypes.c_size_t)]
+
+
+class FrCsr(ctypes.Structure):
+    """pa_fr_csr of the header"""
+    _fields_ = [("row_ptr", _P), ("col", _P), ("val", _P)]

@@ -18,6 +18,7 @@
 #include "../../include/pairing_amd.h"
 #include "env.h"
 #include "launch.h"
+#include "launch_groth16.h"
 #include "launch_msm.h"
 
 namespace {
@@ -1973,6 +1974,353 @@ int pa_fr_ntt_quotient(const pa_fr_ntt_domain* d, const pa_fr* a, const pa_fr* b
         return rc;
     PA_TRY(call_sync(), "kernel execution");
     return download(out, da, bytes);
+}
+
+// ---- R1CS matrices on the device (kernels_r1cs.hip) ----
+// The object owns one allocation on one device: the chunked image of the three
+// matrices (launch_groth16.h).
+struct pa_r1cs {
+    int dev = 0;
+    void* image = nullptr;
+    pa::R1csDev d{};
+};
+
+namespace {
+// r, 4 x u64 LE (fr.rs:4-10)
+const uint64_t kFrModulus[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull,
+                                0x73eda753299d7d48ull};
+bool fr_below_r(const uint64_t* v) {
+    for (int i = 3; i >= 0; i--)
+        if (v[i] != kFrModulus[i]) return v[i] < kFrModulus[i];
+    return false;
+}
+// 0, or the code of what is wrong with one host CSR matrix
+int r1cs_csr_check(const pa_fr_csr* m, size_t n_rows, size_t n_cols) {
+    if (!m) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!m->row_ptr) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (m->row_ptr[0] != 0) return fail(PA_ERR_INVALID_ARGUMENT, "R1CS row_ptr must start at 0");
+    for (size_t r = 0; r < n_rows; r++)
+        if (m->row_ptr[r + 1] < m->row_ptr[r]) return fail(PA_ERR_INVALID_ARGUMENT, "R1CS row_ptr decreases");
+    const uint64_t nnz = m->row_ptr[n_rows];
+    if (nnz >> 32) return fail(PA_ERR_INVALID_ARGUMENT, "R1CS matrices support nnz < 2^32");
+    if (nnz && (!m->col || !m->val)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    for (uint64_t t = 0; t < nnz; t++) {
+        if (m->col[t] >= n_cols) return fail(PA_ERR_INVALID_ARGUMENT, "R1CS column index >= n_cols");
+        if (!fr_below_r(m->val[t].l)) return fail(PA_ERR_INVALID_ARGUMENT, "R1CS coefficient >= r");
+    }
+    return PA_OK;
+}
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+}  // namespace
+
+int pa_r1cs_create(const pa_fr_csr* a, const pa_fr_csr* b, const pa_fr_csr* c, size_t n_rows, size_t n_cols,
+                   pa_r1cs** out) {
+    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    *out = nullptr;
+    if (n_rows > ((size_t)1 << pa::kNttMaxLogN))
+        return fail(PA_ERR_INVALID_ARGUMENT, "R1CS systems support n_rows <= 2^28");
+    const pa_fr_csr* ms[3] = {a, b, c};
+    pa::R1csCsr csr[3];
+    for (int i = 0; i < 3; i++) {
+        if (int rc = r1cs_csr_check(ms[i], n_rows, n_cols)) return rc;
+        csr[i] = {ms[i]->row_ptr, ms[i]->col, (const uint64_t*)ms[i]->val};
+    }
+    pa::R1csImage img;
+    pa::r1cs_build(csr, n_rows, img);
+    const pa::R1csDevLayout lay = pa::r1cs_dev_layout(img);
+    pa_r1cs* r = new pa_r1cs;
+    hipError_t e = hipGetDevice(&r->dev);
+    if (e == hipSuccess) e = hipMalloc(&r->image, lay.bytes ? lay.bytes : 256);
+    uint8_t* base = static_cast<uint8_t*>(r->image);
+    hipStream_t s = call_stream();
+    auto put = [&](size_t off, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, s);
+    };
+    put(lay.val, img.val.data(), img.val.size() * 8);
+    put(lay.col, img.col.data(), img.col.size() * 4);
+    put(lay.slab_off, img.slab_off.data(), img.slab_off.size() * 8);
+    put(lay.slab_len, img.slab_len.data(), img.slab_len.size() * 4);
+    put(lay.chunk_len, img.chunk_len.data(), img.chunk_len.size() * 4);
+    put(lay.chunk_dst, img.chunk_dst.data(), img.chunk_dst.size() * 4);
+    put(lay.fold, img.fold.data(), img.fold.size() * 4);
+    if (e == hipSuccess) e = call_sync();   // the image's host vectors go out of scope below
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        if (r->image) (void)hipFree(r->image);
+        delete r;
+        return fail(hip_code(e), "create R1CS image", e);
+    }
+    r->d = pa::R1csDev{r->image, lay, img.slabs, n_rows, n_cols, img.n_partial, img.n_fold};
+    *out = r;
+    return PA_OK;
+}
+void pa_r1cs_free(pa_r1cs* r) {
+    if (!r) return;
+    if (r->image) (void)hipFree(r->image);
+    delete r;
+}
+size_t pa_r1cs_rows(const pa_r1cs* r) { return r ? r->d.n_rows : 0; }
+size_t pa_r1cs_cols(const pa_r1cs* r) { return r ? r->d.n_cols : 0; }
+size_t pa_r1cs_bytes(const pa_r1cs* r) { return r ? r->d.layout.bytes : 0; }
+size_t pa_r1cs_chunk_len(void) { return pa::kR1csChunkLen; }
+size_t pa_r1cs_eval_workspace_bytes(const pa_r1cs* r, size_t k) { return r ? k * r->d.n_partial * sizeof(pa_fr) : 0; }
+
+namespace {
+// the checks of both evaluation entries that need no pointer
+int r1cs_eval_check(const pa_r1cs* r, unsigned log_n) {
+    if (!r) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (log_n > pa::kNttMaxLogN) return fail(PA_ERR_INVALID_ARGUMENT, "R1CS evaluation supports log_n <= 28");
+    if (((size_t)1 << log_n) < r->d.n_rows)
+        return fail(PA_ERR_INVALID_ARGUMENT, "2^log_n is smaller than the R1CS system's rows");
+    return PA_OK;
+}
+}  // namespace
+
+int pa_r1cs_eval_device(const pa_r1cs* r, const pa_fr* witness, size_t k, unsigned log_n, pa_fr* a, pa_fr* b, pa_fr* c,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = r1cs_eval_check(r, log_n)) return rc;
+    if (k == 0) return PA_OK;
+    if (!a || !b || !c || (r->d.n_cols && !witness)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    const size_t need = pa_r1cs_eval_workspace_bytes(r, k);
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_r1cs_eval_workspace_bytes");
+    int dev = 0;
+    PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
+    if (dev != r->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the R1CS object");
+    PA_TRY(pa::launch_r1cs_eval(r->d, (const uint64_t*)witness, k, log_n, (uint64_t*)a, (uint64_t*)b, (uint64_t*)c,
+                                need ? workspace : nullptr, (hipStream_t)stream),
+           "kernel launch");
+    return PA_OK;
+}
+int pa_r1cs_eval(const pa_r1cs* r, const pa_fr* witness, size_t k, unsigned log_n, pa_fr* a, pa_fr* b, pa_fr* c) {
+    if (int rc = r1cs_eval_check(r, log_n)) return rc;
+    if (k == 0) return PA_OK;
+    if (!a || !b || !c || (r->d.n_cols && !witness)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    DevBuf dw, dabc, dws;
+    int rc;
+    const size_t bytes = (k << log_n) * sizeof(pa_fr);
+    if ((rc = upload(dw, witness, k * r->d.n_cols * sizeof(pa_fr)))) return rc;
+    PA_TRY(dabc.alloc(3 * bytes), "device scratch");
+    const size_t ws = pa_r1cs_eval_workspace_bytes(r, k);
+    PA_TRY(dws.alloc(ws), "device scratch");
+    pa_fr* da = dabc.as<pa_fr>();
+    pa_fr *db = da + (k << log_n), *dc = db + (k << log_n);
+    if ((rc = pa_r1cs_eval_device(r, dw.as<pa_fr>(), k, log_n, da, db, dc, dws.p, ws, call_stream()))) return rc;
+    PA_TRY(call_sync(), "kernel execution");
+    pa_fr* outs[3] = {a, b, c};
+    for (int i = 0; i < 3; i++) {
+        PA_TRY(hipMemcpyAsync(outs[i], da + i * (k << log_n), bytes, hipMemcpyDeviceToHost, dabc.ctx->compute),
+               "D2H copy");
+    }
+    PA_TRY(call_sync(), "D2H copy");
+    return PA_OK;
+}
+
+// ---- Groth16 prover: the proving key as one object, and witness -> proof (kernels_groth16.hip) ----
+struct pa_groth16_pk {
+    int dev = 0;
+    unsigned log_n = 0;
+    size_t n_vars = 0, n_public = 0, h_len = 0;
+    pa_g1_msm_bases *a = nullptr, *b1 = nullptr, *l = nullptr, *h = nullptr;
+    pa_g2_msm_bases* b2 = nullptr;
+    uint64_t* consts = nullptr;   // alpha_g1, beta_g1, delta_g1, beta_g2, delta_g2, the 2^i delta tables (launch_groth16.h)
+};
+
+void pa_groth16_pk_free(pa_groth16_pk* pk) {
+    if (!pk) return;
+    (void)pa_g1_msm_bases_free(pk->a);
+    (void)pa_g1_msm_bases_free(pk->b1);
+    (void)pa_g1_msm_bases_free(pk->l);
+    (void)pa_g1_msm_bases_free(pk->h);
+    (void)pa_g2_msm_bases_free(pk->b2);
+    if (pk->consts) (void)hipFree(pk->consts);
+    delete pk;
+}
+
+int pa_groth16_pk_create(const pa_groth16_key* key, unsigned log_n, pa_groth16_pk** out) {
+    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    *out = nullptr;
+    if (!key) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (log_n > pa::kNttMaxLogN) return fail(PA_ERR_INVALID_ARGUMENT, "Groth16 keys support log_n <= 28");
+    const size_t n = (size_t)1 << log_n, nv = key->n_vars, np = key->n_public;
+    if (np > nv) return fail(PA_ERR_INVALID_ARGUMENT, "n_public exceeds n_vars");
+    if (key->h_len > n) return fail(PA_ERR_INVALID_ARGUMENT, "h_len exceeds 2^log_n");
+    if (nv >= pa::kMsmPreparedMax) return fail(PA_ERR_INVALID_ARGUMENT, "prepared multiexp bases support n < 2^30");
+    if ((nv && (!key->a_query || !key->b_g1_query || !key->b_g2_query)) || (nv > np && !key->l_query) ||
+        (key->h_len && !key->h_query))
+        return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    // the point at infinity as into_affine writes it: (0, 1), flag set
+    pa_g1_affine inf;
+    memset(&inf, 0, sizeof inf);
+    const uint64_t fq_one[6] = {0x760900000002fffdull, 0xebf4000bc40c0002ull, 0x5f48985753c758baull,
+                                0x77ce585370525745ull, 0x5c071a97a256ec6dull, 0x15f65ec3fa80e493ull};
+    memcpy(inf.y.l, fq_one, sizeof fq_one);
+    inf.infinity = 1;
+    std::vector<pa_g1_affine> lq(nv, inf), hq(n, inf);
+    if (nv > np) memcpy(lq.data() + np, key->l_query, (nv - np) * sizeof(pa_g1_affine));
+    if (key->h_len) memcpy(hq.data(), key->h_query, key->h_len * sizeof(pa_g1_affine));
+
+    pa_groth16_pk* pk = new pa_groth16_pk;
+    pk->log_n = log_n;
+    pk->n_vars = nv;
+    pk->n_public = np;
+    pk->h_len = key->h_len;
+    int rc = PA_OK;
+    hipError_t e = hipGetDevice(&pk->dev);
+    if (e != hipSuccess) rc = fail(hip_code(e), "current device", e);
+    if (!rc) rc = pa_g1_msm_bases_prepare(key->a_query, nv, &pk->a);
+    if (!rc) rc = pa_g1_msm_bases_prepare(key->b_g1_query, nv, &pk->b1);
+    if (!rc) rc = pa_g2_msm_bases_prepare(key->b_g2_query, nv, &pk->b2);
+    if (!rc) rc = pa_g1_msm_bases_prepare(lq.data(), nv, &pk->l);
+    if (!rc) rc = pa_g1_msm_bases_prepare(hq.data(), n, &pk->h);
+    if (!rc) {
+        uint64_t host[pa::kGroth16ConstWords];
+        memcpy(host, &key->alpha_g1, 13 * 8);
+        memcpy(host + 13, &key->beta_g1, 13 * 8);
+        memcpy(host + 26, &key->delta_g1, 13 * 8);
+        memcpy(host + 39, &key->beta_g2, 25 * 8);
+        memcpy(host + 64, &key->delta_g2, 25 * 8);
+        // only the flag byte of a record's last word is defined
+        for (size_t w : {12, 25, 38, 63, 88}) host[w] &= 0xff;
+        e = hipMalloc((void**)&pk->consts, pa::kGroth16KeyWords * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMemcpy(pk->consts, host, sizeof host, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = pa::launch_groth16_tables(pk->consts, call_stream());
+        if (e == hipSuccess) e = call_sync();
+        if (e != hipSuccess) rc = fail(hip_code(e), "create Groth16 key", e);
+    }
+    if (rc) {
+        pa_groth16_pk_free(pk);
+        return rc;
+    }
+    *out = pk;
+    return PA_OK;
+}
+int pa_groth16_pk_in_subgroup(const pa_groth16_pk* pk) {
+    return pk && pk->a->in_subgroup && pk->b1->in_subgroup && pk->b2->in_subgroup && pk->l->in_subgroup &&
+                   pk->h->in_subgroup
+               ? 1
+               : 0;
+}
+
+namespace {
+// the prove call's workspace: a, b, c (the quotient overwrites a), the five
+// sums, and one region that the evaluation, the quotient and the multiexps use
+// in turn.  bytes = 0: a batch that one of the steps refuses.
+struct ProveLayout {
+    size_t abc, sums, shared, shared_bytes, msm_bytes[5], bytes;
+};
+ProveLayout prove_layout(const pa_groth16_pk* pk, const pa_r1cs* r, size_t k) {
+    ProveLayout p{};
+    const size_t n = (size_t)1 << pk->log_n, nv = pk->n_vars;
+    // the quotient's workspace for any tile log: 6 arrays of k polynomials cover one pass and several
+    const pa::NttLayout dflt = pa::ntt_layout(pk->log_n, pa::kNttDefaultTileLog);
+    if (k && !pa::ntt_quotient_fits(dflt, k)) return p;
+    const MsmBasesObj* bases[5] = {pk->a, pk->b1, pk->l, pk->h, pk->b2};
+    size_t shared = pa_r1cs_eval_workspace_bytes(r, k);
+    const size_t quot = pk->log_n ? 6 * k * n * sizeof(pa_fr) : 0;
+    shared = shared > quot ? shared : quot;
+    for (int i = 0; i < 5; i++) {
+        const int g = i == 4 ? 2 : 1;
+        const size_t m = i == 3 ? n : nv;
+        const bool glv = bases[i]->in_subgroup != 0;
+        if (k && !pa::msm_prepared_batch_fits(m, k, glv, g)) return p;
+        p.msm_bytes[i] = m && k ? pa::msm_prepared_batch_workspace_bytes(m, k, glv, g) : 0;
+        shared = shared > p.msm_bytes[i] ? shared : p.msm_bytes[i];
+    }
+    size_t o = 0;
+    p.abc = o;    o = align256(o + 3 * k * n * sizeof(pa_fr));
+    p.sums = o;   o = align256(o + k * (4 * sizeof(pa_g1) + sizeof(pa_g2)));
+    p.shared = o; o = align256(o + shared);
+    p.shared_bytes = shared;
+    p.bytes = o ? o : 256;
+    return p;
+}
+// what both prove entries refuse before touching memory
+int prove_check(const pa_groth16_pk* pk, const pa_r1cs* r, const pa_fr_ntt_domain* d, size_t k) {
+    if (!pk || !r || !d) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (d->layout.log_n != pk->log_n)
+        return fail(PA_ERR_INVALID_ARGUMENT, "the NTT domain's log_n differs from the Groth16 key's");
+    if (r->d.n_cols != pk->n_vars)
+        return fail(PA_ERR_INVALID_ARGUMENT, "the R1CS system's columns differ from the Groth16 key's n_vars");
+    if (r->d.n_rows > ((size_t)1 << pk->log_n))
+        return fail(PA_ERR_INVALID_ARGUMENT, "the R1CS system has more rows than the domain has points");
+    if (r->dev != pk->dev || d->dev != pk->dev)
+        return fail(PA_ERR_INVALID_ARGUMENT, "the Groth16 key, the R1CS object and the NTT domain are on different devices");
+    if (k && (prove_layout(pk, r, k).bytes == 0 || !pa::ntt_quotient_fits(d->layout, k)))
+        return fail(PA_ERR_INVALID_ARGUMENT,
+                    "Groth16 batch over a multiexp's 32-bit item limit or the quotient's grid limit: split it");
+    return PA_OK;
+}
+}  // namespace
+
+size_t pa_groth16_prove_workspace_bytes(const pa_groth16_pk* pk, const pa_r1cs* r1cs, size_t k) {
+    if (!pk || !r1cs || r1cs->d.n_cols != pk->n_vars || r1cs->d.n_rows > ((size_t)1 << pk->log_n)) return 0;
+    return prove_layout(pk, r1cs, k).bytes;
+}
+
+int pa_groth16_prove_device(const pa_groth16_pk* pk, const pa_r1cs* r1cs, const pa_fr_ntt_domain* d,
+                            const pa_fr* witness, const pa_fr* dev_r, const pa_fr* dev_s, size_t k,
+                            pa_groth16_proof* proofs, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = prove_check(pk, r1cs, d, k)) return rc;
+    if (k == 0) return PA_OK;
+    if (!dev_r || !dev_s || !proofs || !workspace || (pk->n_vars && !witness))
+        return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    const ProveLayout p = prove_layout(pk, r1cs, k);
+    if (workspace_bytes < p.bytes || pa::ntt_quotient_workspace_bytes(d->layout, k) > p.shared_bytes)
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_groth16_prove_workspace_bytes");
+    int dev = 0;
+    PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
+    if (dev != pk->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the Groth16 key");
+    const size_t n = (size_t)1 << pk->log_n, nv = pk->n_vars;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    pa_fr* a = reinterpret_cast<pa_fr*>(ws + p.abc);
+    pa_fr *b = a + k * n, *c = b + k * n;
+    pa_g1* sums = reinterpret_cast<pa_g1*>(ws + p.sums);   // S_a, S_b1, S_l, S_h (k each), then S_b2
+    pa_g2* sum_b2 = reinterpret_cast<pa_g2*>(sums + 4 * k);
+    void* shared = ws + p.shared;
+    int rc;
+    if ((rc = pa_r1cs_eval_device(r1cs, witness, k, pk->log_n, a, b, c, shared, p.shared_bytes, stream))) return rc;
+    if ((rc = pa_fr_ntt_quotient_device(d, a, b, c, a, k, shared, p.shared_bytes, stream))) return rc;
+    const unsigned mont = PA_MSM_SCALARS_MONTGOMERY;
+    if ((rc = pa_g1_multiexp_prepared_batch_device(pk->a, witness, nv, k, mont, sums, shared, p.shared_bytes, stream)))
+        return rc;
+    if ((rc = pa_g1_multiexp_prepared_batch_device(pk->b1, witness, nv, k, mont, sums + k, shared, p.shared_bytes,
+                                                   stream)))
+        return rc;
+    if ((rc = pa_g1_multiexp_prepared_batch_device(pk->l, witness, nv, k, mont, sums + 2 * k, shared, p.shared_bytes,
+                                                   stream)))
+        return rc;
+    if ((rc = pa_g1_multiexp_prepared_batch_device(pk->h, a, n, k, mont, sums + 3 * k, shared, p.shared_bytes, stream)))
+        return rc;
+    if ((rc = pa_g2_multiexp_prepared_batch_device(pk->b2, witness, nv, k, mont, sum_b2, shared, p.shared_bytes,
+                                                   stream)))
+        return rc;
+    PA_TRY(pa::launch_groth16_assemble(pk->consts, (const uint64_t*)sums, (const uint64_t*)(sums + k),
+                                       (const uint64_t*)(sums + 2 * k), (const uint64_t*)(sums + 3 * k),
+                                       (const uint64_t*)sum_b2, (const uint64_t*)dev_r, (const uint64_t*)dev_s, k,
+                                       (uint64_t*)proofs, (hipStream_t)stream),
+           "kernel launch");
+    return PA_OK;
+}
+
+int pa_groth16_prove(const pa_groth16_pk* pk, const pa_r1cs* r1cs, const pa_fr_ntt_domain* d, const pa_fr* witness,
+                     const pa_fr* host_r, const pa_fr* host_s, size_t k, pa_groth16_proof* proofs) {
+    if (int rc = prove_check(pk, r1cs, d, k)) return rc;
+    if (k == 0) return PA_OK;
+    if (!host_r || !host_s || !proofs || (pk->n_vars && !witness)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    DevBuf dw, dr, ds, dout, dws;
+    int rc;
+    if ((rc = upload(dw, witness, k * pk->n_vars * sizeof(pa_fr)))) return rc;
+    if ((rc = upload(dr, host_r, k * sizeof(pa_fr)))) return rc;
+    if ((rc = upload(ds, host_s, k * sizeof(pa_fr)))) return rc;
+    PA_TRY(dout.alloc(k * sizeof(pa_groth16_proof)), "device scratch");
+    const size_t ws = prove_layout(pk, r1cs, k).bytes;
+    PA_TRY(dws.alloc(ws), "device scratch");
+    if ((rc = pa_groth16_prove_device(pk, r1cs, d, dw.as<pa_fr>(), dr.as<pa_fr>(), ds.as<pa_fr>(), k,
+                                      dout.as<pa_groth16_proof>(), dws.p, ws, call_stream())))
+        return rc;
+    PA_TRY(call_sync(), "kernel execution");
+    return download(proofs, dout, k * sizeof(pa_groth16_proof));
 }
 
 // ---- CurveProjective / CurveAffine surface, G1 and G2 (kernels_group.hip) ----

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, FrNttDomain, G1MsmBases, G2MsmBases, _lib, call, csr_offsets, msm_bases, msm_scalars, ntt_mode
+from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, W_PROOF, FrNttDomain, G1MsmBases, G2MsmBases, Groth16Pk, R1cs, _lib, call, csr_offsets, msm_bases, msm_scalars, ntt_mode
 
 
 def _stream_ptr(stream):
@@ -361,6 +361,64 @@ def fr_ntt_quotient(domain, a, b, c, out, workspace=None, stream=None):
     ws = _words(workspace, need, "workspace") if need else ctypes.c_void_p(0)
     args = (_dptr(a, 4, "a"), _dptr(b, 4, "b"), _dptr(c, 4, "c"), _dptr(out, 4, "out"))
     call("pa_fr_ntt_quotient_device", h, *args, batch, ws, need * 8, _stream_ptr(stream))
+
+
+def r1cs_eval_workspace_words(system, k):
+    """int64 words of `workspace` for r1cs_eval over k witnesses (0 for a system without rows of several chunks)."""
+    if not isinstance(system, R1cs):
+        raise ValueError("system must come from r1cs()")
+    return (system.eval_workspace_bytes(k) + 7) // 8
+
+
+def r1cs_eval(system, witness, log_n, a, b, c, workspace=None, stream=None):
+    """The products of the system's matrices with the k witnesses of `witness` ((k * cols, 4)
+    int64 Montgomery Fr rows end to end) into the first k * 2^log_n rows of a, b and c
+    ((rows, 4) int64, the layout fr_ntt_quotient takes); rows from the system's rows up to
+    2^log_n are written as zero.  workspace: an int64 buffer of
+    r1cs_eval_workspace_words(system, k), not needed where that is 0.  Nothing is
+    allocated or read back."""
+    if not isinstance(system, R1cs):
+        raise ValueError("system must come from r1cs()")
+    system.handle()   # a closed object is rejected first
+    if system.cols == 0:
+        raise ValueError("a system of no columns has no device witness: use the host entry")
+    h, k, log_n = system.check_eval(witness.shape[0], None, log_n)
+    for t, name in ((a, "a"), (b, "b"), (c, "c")):
+        _rows(t, k << log_n, name)
+    args = (_dptr(witness, 4, "witness"), k, log_n, _dptr(a, 4, "a"), _dptr(b, 4, "b"), _dptr(c, 4, "c"))
+    need = r1cs_eval_workspace_words(system, k)
+    if need and workspace is None:
+        raise ValueError("workspace must be a contiguous int64 CUDA tensor of >= %d words" % need)
+    ws = _words(workspace, need, "workspace") if need else ctypes.c_void_p(0)
+    call("pa_r1cs_eval_device", h, *args, ws, need * 8, _stream_ptr(stream))
+
+
+def groth16_prove_workspace(pk, system, k, device):
+    """A device workspace sized for groth16_prove over k proofs.  A batch over a multiexp's
+    32-bit item limit (include/pairing_amd.h) is a ValueError: split it."""
+    if not isinstance(pk, Groth16Pk):
+        raise ValueError("pk must come from groth16_pk")
+    return torch.empty(pk.prove_workspace_bytes(system, k), dtype=torch.uint8, device=device)
+
+
+def groth16_prove(pk, system, domain, witness, r, s, out, workspace, stream=None):
+    """k Groth16 proofs into the first k rows of `out` ((rows, 51) int64: the affine records
+    A, B, C of pa_groth16_proof): witness (k * n_vars, 4), r and s (k, 4) int64 Montgomery
+    Fr rows in HBM, workspace from groth16_prove_workspace.  The evaluation, the quotient,
+    the five multiexps and the assembly are enqueued on the stream; nothing is allocated,
+    synchronized or read back."""
+    if not isinstance(pk, Groth16Pk):
+        raise ValueError("pk must come from groth16_pk")
+    pk.handle()   # a closed object is rejected first
+    (h, hr, hd), k = pk.check_prove(system, domain, witness.shape[0], r.shape[0], s.shape[0])
+    _rows(out, k, "out")
+    need = pk.prove_workspace_bytes(system, k)
+    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.dtype != torch.uint8 \
+            or workspace.numel() < need:
+        raise ValueError("workspace must be a contiguous uint8 CUDA tensor of >= %d bytes" % need)
+    args = (_dptr(witness, 4, "witness"), _dptr(r, 4, "r"), _dptr(s, 4, "s"))
+    call("pa_groth16_prove_device", h, hr, hd, *args, k, _dptr(out, W_PROOF, "out"),
+         ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
 
 
 def multiexp_workspace(group, n, device):
