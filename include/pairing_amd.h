@@ -687,6 +687,111 @@ int pa_groth16_prove(const pa_groth16_pk *pk, const pa_r1cs *r1cs, const pa_fr_n
                      const pa_fr *host_witness, const pa_fr *host_r, const pa_fr *host_s, size_t k,
                      pa_groth16_proof *proofs);   /* host memory */
 
+/* ---- Groth16 verifier: k proofs per call over a prepared verifying key ----
+ * bellman's prepare_verifying_key and verify_proof.  For proof j with public
+ * inputs x_1 .. x_l, l = n_public - 1 (n_public counts the constant one, as in
+ * pa_groth16_key):
+ *   acc_j   = ic[0] + sum_{i = 1..l} x_{j,i} ic[i]
+ *   gt_j    = final_exponentiation(ML(A_j, B_j) ML(acc_j, -gamma) ML(C_j, -delta))
+ *   valid_j = (the final exponentiation is not None) && gt_j == e(alpha, beta)
+ * gt and valid are canonical, so they are bit-exact whichever kernels run.
+ *
+ * The key object lives on the device that was current at creation.  It holds
+ * e(alpha, beta), -gamma and -delta as affine and as pa_g2_prepared records,
+ * ic[0], and for each of ic[1..l] one fixed-base comb table
+ * (pa_g1_fixed_base_table_words() u64, about 0.49 MB; exact digits).  l is at
+ * most PA_GROTH16_VK_MAX_INPUTS (the tables then take 250 MB); creation above
+ * it, with n_public == 0 or with a NULL pointer returns
+ * PA_ERR_INVALID_ARGUMENT.  Creation waits for the tables.  alpha, beta, gamma
+ * and delta are taken as they are (no curve or subgroup test).  ic points may
+ * be the point at infinity, and may lie on the curve outside G1: the comb
+ * assumes no subgroup, and the sum is the reference's as long as no ic point
+ * has an order below 129 (the table holds d ic[i] for d <= 128; E(Fq) has such
+ * points, of order 3, 11, 33 and 121, none of them in G1).  ic points off the
+ * curve are undefined.  The object may be used from any host thread and lives
+ * until pa_groth16_vk_free (NULL is a no-op); work that reads it must have
+ * completed before it is freed.
+ *
+ * Inputs are rows of 4 u64: pa_fr_repr with PA_MSM_SCALARS_REPR, pa_fr
+ * (Montgomery, the prover's witness format) with PA_MSM_SCALARS_MONTGOMERY.
+ * Row i of proof j is inputs[j * input_stride + i], i < l, input_stride >= l:
+ * with inputs = witness + 1 and input_stride = n_vars the proofs of
+ * pa_groth16_prove_device are verified from the witness buffer as it lies.  A
+ * row that is not below r is undefined.  With l = 0 inputs may be NULL.
+ *
+ * pa_groth16_vk_input_sum*: acc_j alone, k affine records (what into_affine
+ * gives for the reference's sum, infinity included).
+ *
+ * pa_groth16_verify*: proofs are the 51-word records the prover writes; the
+ * points are taken as they are, like pa_pairing_batch takes its points.
+ * valid: k bytes, 1 or 0.  gt may be NULL; where the final exponentiation is
+ * None, gt_j is a zero record and valid_j = 0.
+ *
+ * pa_groth16_verify_encoded*: k records of 192 bytes, A (48), B (96) and C
+ * (48) compressed as bellman's Proof::write lays them out, through the checked
+ * decoders (pa_g{1,2}_decode_batch, compressed = 1, checked = 1).  status: 3 k
+ * bytes, the PA_DECODE_* codes of A, B and C of proof j at status[3 j ..
+ * 3 j + 2].  A proof with a nonzero status has valid = 0; its gt is what the
+ * chain gives for the decoders' output (the point at infinity for a failed
+ * record) and is meaningful only where all three statuses are PA_DECODE_OK.
+ *
+ * The device entries take device pointers, enqueue everything on `stream`,
+ * allocate nothing (the generated kernels' workspace pool is theirs), stage
+ * nothing from the host and do not synchronize.  Up to
+ * PA_GROTH16_VERIFY_SHARED_MIN - 1 proofs all 3 k pairs run through the
+ * e(P, Q) Miller loops against the affine -gamma and -delta (the cooperative
+ * and lane-group kernels then serve a small batch); from there on (acc, -gamma)
+ * and (C, -delta) run on the shared-prepared Miller loop, which does no G2
+ * arithmetic per pair but is one launch of one lane per pairing for each of
+ * the two points (measured: slower at 32768 proofs, faster at 65536, nothing
+ * between; profiles/groth16_verify/).  The environment variable
+ * PA_G16V_SHARED_MIN overrides the bound (read at every call; tests and
+ * measurements).  The workspace begins with the P array (3 k pa_g1_affine:
+ * A | acc | C) and, at the next multiple of 256 bytes, the Q array (3 k
+ * pa_g2_affine: B, then -gamma and -delta k times each, which only the
+ * 3 k-pair path writes); the rest is scratch.  workspace:
+ * pa_groth16_verify_workspace_bytes(vk, k) bytes for either verify entry
+ * (monotone in k; 0 for a NULL key or k above PA_GROTH16_VERIFY_MAX_BATCH, which
+ * the entries refuse: split the batch), pa_groth16_vk_input_sum_workspace_bytes
+ * for the sum alone (k l Jacobian records; with l = 0 workspace may be NULL).
+ * Errors, all PA_ERR_INVALID_ARGUMENT before anything runs: a NULL pointer,
+ * input_stride < l, unknown flag bits, key and stream on different devices, a
+ * batch over the limit, a workspace that is too small.  k = 0 writes nothing. */
+#define PA_GROTH16_VK_MAX_INPUTS 512
+#define PA_GROTH16_VERIFY_MAX_BATCH ((size_t)1 << 24)
+#define PA_GROTH16_VERIFY_SHARED_MIN 65536
+#define PA_GROTH16_ENCODED_PROOF_BYTES 192
+typedef struct {
+    pa_g1_affine alpha_g1;
+    pa_g2_affine beta_g2, gamma_g2, delta_g2;
+    const pa_g1_affine *ic;   /* n_public records */
+    size_t n_public;
+} pa_groth16_vkey;   /* host memory */
+typedef struct pa_groth16_vk pa_groth16_vk;
+int pa_groth16_vk_create(const pa_groth16_vkey *key, pa_groth16_vk **out);
+void pa_groth16_vk_free(pa_groth16_vk *vk);   /* NULL is a no-op */
+size_t pa_groth16_vk_n_public(const pa_groth16_vk *vk);
+size_t pa_groth16_vk_bytes(const pa_groth16_vk *vk);   /* device memory it holds */
+size_t pa_groth16_vk_input_sum_workspace_bytes(const pa_groth16_vk *vk, size_t k);
+int pa_groth16_vk_input_sum_device(const pa_groth16_vk *vk, const pa_fr *dev_inputs, size_t input_stride,
+                                   unsigned flags, size_t k, pa_g1_affine *dev_out, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+int pa_groth16_vk_input_sum(const pa_groth16_vk *vk, const pa_fr *host_inputs, size_t input_stride, unsigned flags,
+                            size_t k, pa_g1_affine *out);   /* host memory */
+size_t pa_groth16_verify_workspace_bytes(const pa_groth16_vk *vk, size_t k);
+int pa_groth16_verify_device(const pa_groth16_vk *vk, const pa_groth16_proof *dev_proofs, const pa_fr *dev_inputs,
+                             size_t input_stride, unsigned flags, size_t k, uint8_t *dev_valid, pa_fq12 *dev_gt,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int pa_groth16_verify(const pa_groth16_vk *vk, const pa_groth16_proof *proofs, const pa_fr *inputs,
+                      size_t input_stride, unsigned flags, size_t k, uint8_t *valid, pa_fq12 *gt);   /* host memory */
+int pa_groth16_verify_encoded_device(const pa_groth16_vk *vk, const uint8_t *dev_enc, const pa_fr *dev_inputs,
+                                     size_t input_stride, unsigned flags, size_t k, uint8_t *dev_valid,
+                                     uint8_t *dev_status, pa_fq12 *dev_gt, void *workspace, size_t workspace_bytes,
+                                     void *stream);
+int pa_groth16_verify_encoded(const pa_groth16_vk *vk, const uint8_t *enc, const pa_fr *inputs, size_t input_stride,
+                              unsigned flags, size_t k, uint8_t *valid, uint8_t *status,
+                              pa_fq12 *gt);   /* host memory */
+
 /* ---- device-resident variants (pointers are device memory) ---- */
 int pa_g1_decode_batch_device(const uint8_t *enc, size_t n, int compressed, int checked, pa_g1_affine *out,
                               uint8_t *status, void *stream);

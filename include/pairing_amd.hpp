@@ -821,6 +821,78 @@ private:
     FrNttDomain domain_;
 };
 
+// A Groth16 verifier: the verifying key prepared on the device (pa_groth16_vk).
+// verify() checks k proofs in one call; the inputs are k vectors of n_inputs()
+// rows end to end, Montgomery (the witness format) unless montgomery = false.
+// Move-only.
+class Groth16Verifier {
+public:
+    struct EncodedResult {   // valid: k bytes; status: the PA_DECODE_* codes of A, B, C of proof j at 3 j .. 3 j + 2
+        std::vector<uint8_t> valid, status;
+    };
+    explicit Groth16Verifier(const pa_groth16_vkey& key) { check(pa_groth16_vk_create(&key, &vk_), "Groth16Verifier"); }
+    Groth16Verifier(const Groth16Verifier&) = delete;
+    Groth16Verifier& operator=(const Groth16Verifier&) = delete;
+    Groth16Verifier(Groth16Verifier&& o) noexcept : vk_(o.vk_) { o.vk_ = nullptr; }
+    Groth16Verifier& operator=(Groth16Verifier&& o) noexcept {
+        if (this != &o) {
+            pa_groth16_vk_free(vk_);
+            vk_ = o.vk_;
+            o.vk_ = nullptr;
+        }
+        return *this;
+    }
+    ~Groth16Verifier() { pa_groth16_vk_free(vk_); }
+
+    const pa_groth16_vk* get() const { return vk_; }
+    size_t n_public() const { return pa_groth16_vk_n_public(vk_); }
+    size_t n_inputs() const { return n_public() - 1; }
+    // valid[j] = 1 iff proof j verifies; gt (optional) gets the k pairing-product values
+    std::vector<uint8_t> verify(const std::vector<pa_groth16_proof>& proofs, const std::vector<pa_fr>& inputs, size_t k,
+                                bool montgomery = true, std::vector<pa_fq12>* gt = nullptr) const {
+        if (proofs.size() != k) throw std::invalid_argument("Groth16Verifier::verify: proofs are not k records");
+        sized(inputs, k, "Groth16Verifier::verify");
+        std::vector<uint8_t> valid(k);
+        if (gt) gt->resize(k);
+        check(pa_groth16_verify(vk_, proofs.data(), inputs.data(), n_inputs(), flags(montgomery), k, valid.data(),
+                                gt ? gt->data() : nullptr),
+              "Groth16Verifier::verify");
+        return valid;
+    }
+    // proofs off the wire: k records of PA_GROTH16_ENCODED_PROOF_BYTES (A, B, C compressed)
+    EncodedResult verify_encoded(const std::vector<uint8_t>& bytes, const std::vector<pa_fr>& inputs, size_t k,
+                                 bool montgomery = true, std::vector<pa_fq12>* gt = nullptr) const {
+        if (bytes.size() != k * PA_GROTH16_ENCODED_PROOF_BYTES)
+            throw std::invalid_argument("Groth16Verifier::verify_encoded: bytes are not k records of 192");
+        sized(inputs, k, "Groth16Verifier::verify_encoded");
+        EncodedResult r;
+        r.valid.resize(k);
+        r.status.resize(3 * k);
+        if (gt) gt->resize(k);
+        check(pa_groth16_verify_encoded(vk_, bytes.data(), inputs.data(), n_inputs(), flags(montgomery), k,
+                                        r.valid.data(), r.status.data(), gt ? gt->data() : nullptr),
+              "Groth16Verifier::verify_encoded");
+        return r;
+    }
+    // ic[0] + sum_i x_i ic[i] for each of the k input vectors, as affine records
+    std::vector<pa_g1_affine> input_sum(const std::vector<pa_fr>& inputs, size_t k, bool montgomery = true) const {
+        sized(inputs, k, "Groth16Verifier::input_sum");
+        std::vector<pa_g1_affine> out(k);
+        check(pa_groth16_vk_input_sum(vk_, inputs.data(), n_inputs(), flags(montgomery), k, out.data()),
+              "Groth16Verifier::input_sum");
+        return out;
+    }
+
+private:
+    static unsigned flags(bool montgomery) { return montgomery ? PA_MSM_SCALARS_MONTGOMERY : PA_MSM_SCALARS_REPR; }
+    void sized(const std::vector<pa_fr>& inputs, size_t k, const char* what) const {
+        if (inputs.size() != k * n_inputs())
+            throw std::invalid_argument(std::string(what) + ": inputs are not k vectors of n_inputs() rows");
+    }
+    pa_groth16_vk* vk_ = nullptr;
+};
+inline Groth16Verifier verifier(const pa_groth16_vkey& key) { return Groth16Verifier(key); }
+
 using G1Uncompressed = Encoded<G1Affine, 1, false>;
 using G1Compressed = Encoded<G1Affine, 1, true>;
 using G2Uncompressed = Encoded<G2Affine, 2, false>;

@@ -17,7 +17,8 @@ Device-resident entry points for torch tensors live in `pairing_amd.device`.
 import numpy as np
 
 from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, NTT_MAX_LOG_N, FrNttDomain, G1MsmBases, G2MsmBases,
-                      FrCsr, Groth16Key, Groth16Pk, R1cs, R1CS_CHUNK_LEN, W_PROOF,
+                      FrCsr, Groth16Key, Groth16Pk, Groth16VKey, Groth16Vk, GROTH16_VK_MAX_INPUTS, GROTH16_ENCODED_PROOF_BYTES,
+                      R1cs, R1CS_CHUNK_LEN, W_PROOF,
                       PairingError, _lib, as_rows, batch_shape, call, csr_offsets, device_count, msm_bases, msm_scalars, ntt_mode, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
 
 __all__ = [
@@ -38,6 +39,7 @@ __all__ = [
     "G2MsmBases", "g2_msm_prepare", "g2_multiexp_prepared", "g2_multiexp_prepared_batch",
     "FrNttDomain", "fr_ntt_domain", "fr_ntt", "fr_ntt_quotient",
     "R1cs", "r1cs", "r1cs_eval", "R1CS_CHUNK_LEN", "Groth16Pk", "groth16_pk", "groth16_prove",
+    "Groth16Vk", "groth16_vk", "groth16_verify", "groth16_verify_encoded", "groth16_input_sum",
     "g1_eq", "g2_eq", "g1_double", "g2_double", "g1_add", "g2_add", "g1_add_mixed", "g2_add_mixed", "g1_negate", "g2_negate",
     "g1_sub", "g2_sub", "g1_into_affine", "g2_into_affine", "g1_into_projective", "g2_into_projective",
     "g2_batch_normalization", "g2_wnaf_fixed_base",
@@ -856,6 +858,91 @@ def groth16_prove(pk, system, domain, witness, r, s):
     if k:
         call("pa_groth16_prove", h, hr, hd, ptr(w), ptr(r), ptr(s), k, ptr(out))
     return out
+
+
+def groth16_vk(alpha_g1, beta_g2, gamma_g2, delta_g2, ic):
+    """A verifying key prepared on the current device (pa_groth16_vk_create): alpha_g1 (1, 13),
+    beta_g2, gamma_g2, delta_g2 (1, 25) affine records and ic (n_public, 13), n_public >= 1
+    counting the constant one.  Returns a Groth16Vk."""
+    import ctypes
+    singles = [as_rows(x, w, name) for x, w, name in ((alpha_g1, W_G1A, "alpha_g1"), (beta_g2, W_G2A, "beta_g2"),
+                                                      (gamma_g2, W_G2A, "gamma_g2"), (delta_g2, W_G2A, "delta_g2"))]
+    for x, name in zip(singles, ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2")):
+        if x.shape[0] != 1:
+            raise ValueError("%s must be one affine record, got %d" % (name, x.shape[0]))
+    icq = as_rows(ic, W_G1A, "ic") if len(ic) else np.zeros((0, W_G1A), np.uint64)
+    if icq.shape[0] < 1 or icq.shape[0] - 1 > GROTH16_VK_MAX_INPUTS:
+        raise ValueError("ic must have n_public = 1..%d rows, got %d" % (GROTH16_VK_MAX_INPUTS + 1, icq.shape[0]))
+    key = Groth16VKey()
+    for field, x in zip(("alpha_g1", "beta_g2", "gamma_g2", "delta_g2"), singles):
+        ctypes.memmove(getattr(key, field), x.ctypes.data, x.nbytes)
+    key.ic, key.n_public = icq.ctypes.data, icq.shape[0]
+    h = ctypes.c_void_p(0)
+    call("pa_groth16_vk_create", ctypes.byref(key), ctypes.byref(h))
+    return Groth16Vk._adopt(h)
+
+
+def _vk_inputs(vk, inputs, k, stride, montgomery):
+    """(handle, input rows, stride, flag) of a call over k proofs; k None: as many as the rows hold"""
+    if not isinstance(vk, Groth16Vk):
+        raise ValueError("vk must come from groth16_vk")
+    vk.handle()   # a closed object is rejected first
+    flag = msm_scalars(montgomery)
+    x = as_rows(inputs, W_FR, "inputs") if inputs is not None and len(inputs) else np.zeros((0, W_FR), np.uint64)
+    if k is None:
+        if vk.n_inputs == 0:
+            raise ValueError("a key without inputs needs k")
+        per = vk.n_inputs if stride is None else int(stride)
+        if per < vk.n_inputs:
+            raise ValueError("input stride %d is below the key's %d inputs" % (per, vk.n_inputs))
+        k = (x.shape[0] + per - vk.n_inputs) // per if x.shape[0] >= vk.n_inputs else 0
+    h, stride = vk.check_inputs(x.shape[0], k, stride)
+    return h, x, int(k), stride, flag
+
+
+def groth16_input_sum(vk, inputs, k=None, stride=None, montgomery=True):
+    """The public-input sums of k proofs (pa_groth16_vk_input_sum): (k, 13) affine records
+    ic[0] + sum_i x_i ic[i].  inputs: (rows, 4) rows, Montgomery Fr (montgomery=True) or FrRepr,
+    row i of proof j at j * stride + i (stride None: n_inputs rows per proof, end to end)."""
+    h, x, k, stride, flag = _vk_inputs(vk, inputs, k, stride, montgomery)
+    out = np.zeros((k, W_G1A), np.uint64)
+    if k:
+        call("pa_groth16_vk_input_sum", h, ptr(x), stride, flag, k, ptr(out))
+    return out
+
+
+def groth16_verify(vk, proofs, inputs, montgomery=True, return_gt=False, stride=None):
+    """k Groth16 proofs checked in one call (pa_groth16_verify): proofs (k, 51) rows as
+    groth16_prove writes them, inputs as for groth16_input_sum.  Returns a (k,) bool array, or
+    (valid, gt) with return_gt=True: gt (k, 72) = final_exponentiation(ML(A, B) ML(acc, -gamma)
+    ML(C, -delta)), a zero row where that is None."""
+    pr = as_rows(proofs, W_PROOF, "proofs") if len(proofs) else np.zeros((0, W_PROOF), np.uint64)
+    h, x, k, stride, flag = _vk_inputs(vk, inputs, pr.shape[0], stride, montgomery)
+    valid = np.zeros(k, np.uint8)
+    gt = np.zeros((k, W_FQ12), np.uint64) if return_gt else None
+    if k:
+        call("pa_groth16_verify", h, ptr(pr), ptr(x), stride, flag, k, ptr(valid), ptr(gt) if return_gt else None)
+    return (valid.astype(bool), gt) if return_gt else valid.astype(bool)
+
+
+def groth16_verify_encoded(vk, data, inputs, montgomery=True, return_gt=False, stride=None):
+    """groth16_verify for proofs off the wire (pa_groth16_verify_encoded): data (k, 192) uint8, A, B
+    and C compressed in bellman's Proof::write order, through the checked decoders.  Returns
+    (valid, status) or (valid, status, gt): status (k, 3) uint8 DECODE_STATUS codes of A, B, C;
+    a proof with a nonzero status is not valid and its gt is meaningless."""
+    enc = np.ascontiguousarray(np.asarray(data, dtype=np.uint8))
+    if enc.ndim == 1:
+        enc = enc.reshape(-1, GROTH16_ENCODED_PROOF_BYTES) if enc.size % GROTH16_ENCODED_PROOF_BYTES == 0 else enc
+    if enc.ndim != 2 or enc.shape[1] != GROTH16_ENCODED_PROOF_BYTES:
+        raise ValueError("encoded proofs must have shape (k, %d), got %s" % (GROTH16_ENCODED_PROOF_BYTES, enc.shape))
+    h, x, k, stride, flag = _vk_inputs(vk, inputs, enc.shape[0], stride, montgomery)
+    valid = np.zeros(k, np.uint8)
+    status = np.zeros((k, 3), np.uint8)
+    gt = np.zeros((k, W_FQ12), np.uint64) if return_gt else None
+    if k:
+        call("pa_groth16_verify_encoded", h, ptr(enc), ptr(x), stride, flag, k, ptr(valid), ptr(status),
+             ptr(gt) if return_gt else None)
+    return (valid.astype(bool), status, gt) if return_gt else (valid.astype(bool), status)
 
 
 # ---- CurveProjective / CurveAffine surface for G1 and G2 (ec.rs:1-621) ----

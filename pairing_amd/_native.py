@@ -230,6 +230,17 @@ _SIGS.update({
     "pa_groth16_prove_workspace_bytes": [_P, _P, _N],   # returns size_t (below)
     "pa_groth16_prove_device": [_P, _P, _P, _P, _P, _P, _N, _P, _P, _N, _P],
     "pa_groth16_prove": [_P, _P, _P, _P, _P, _P, _N, _P],
+    "pa_groth16_vk_create": [_P, ctypes.POINTER(_P)],
+    "pa_groth16_vk_n_public": [_P],                     # these four return size_t (below)
+    "pa_groth16_vk_bytes": [_P],
+    "pa_groth16_vk_input_sum_workspace_bytes": [_P, _N],
+    "pa_groth16_verify_workspace_bytes": [_P, _N],
+    "pa_groth16_vk_input_sum_device": [_P, _P, _N, ctypes.c_uint, _N, _P, _P, _N, _P],
+    "pa_groth16_vk_input_sum": [_P, _P, _N, ctypes.c_uint, _N, _P],
+    "pa_groth16_verify_device": [_P, _P, _P, _N, ctypes.c_uint, _N, _P, _P, _P, _N, _P],
+    "pa_groth16_verify": [_P, _P, _P, _N, ctypes.c_uint, _N, _P, _P],
+    "pa_groth16_verify_encoded_device": [_P, _P, _P, _N, ctypes.c_uint, _N, _P, _P, _P, _P, _N, _P],
+    "pa_groth16_verify_encoded": [_P, _P, _P, _N, ctypes.c_uint, _N, _P, _P, _P],
 })
 for _name, _args in _SIGS.items():
     _fn = getattr(_lib, _name)
@@ -256,10 +267,11 @@ for _name in ("pa_fr_ntt_domain_bytes", "pa_fr_ntt_polys_per_workgroup", "pa_fr_
               "pa_fr_ntt_quotient_workspace_bytes"):
     getattr(_lib, _name).restype = ctypes.c_size_t
 for _name in ("pa_r1cs_rows", "pa_r1cs_cols", "pa_r1cs_bytes", "pa_r1cs_eval_workspace_bytes", "pa_r1cs_chunk_len",
-              "pa_groth16_prove_workspace_bytes"):
+              "pa_groth16_prove_workspace_bytes", "pa_groth16_vk_n_public", "pa_groth16_vk_bytes",
+              "pa_groth16_vk_input_sum_workspace_bytes", "pa_groth16_verify_workspace_bytes"):
     getattr(_lib, _name).restype = ctypes.c_size_t
 _lib.pa_r1cs_chunk_len.argtypes = []
-for _name in ("pa_r1cs_free", "pa_groth16_pk_free"):
+for _name in ("pa_r1cs_free", "pa_groth16_pk_free", "pa_groth16_vk_free"):
     getattr(_lib, _name).argtypes = [_P]
     getattr(_lib, _name).restype = None
 
@@ -669,6 +681,72 @@ class Groth16Key(ctypes.Structure):
                 ("delta_g2", ctypes.c_uint64 * W_G2A), ("n_vars", ctypes.c_size_t), ("n_public", ctypes.c_size_t),
                 ("a_query", _P), ("b_g1_query", _P), ("b_g2_query", _P), ("l_query", _P), ("h_query", _P),
                 ("h_len", ctypes.c_size_t)]
+
+
+GROTH16_VK_MAX_INPUTS = 512        # PA_GROTH16_VK_MAX_INPUTS of the header
+GROTH16_ENCODED_PROOF_BYTES = 192  # PA_GROTH16_ENCODED_PROOF_BYTES: A (48), B (96), C (48) compressed
+
+
+class Groth16VKey(ctypes.Structure):
+    """pa_groth16_vkey of the header"""
+    _fields_ = [("alpha_g1", ctypes.c_uint64 * W_G1A), ("beta_g2", ctypes.c_uint64 * W_G2A),
+                ("gamma_g2", ctypes.c_uint64 * W_G2A), ("delta_g2", ctypes.c_uint64 * W_G2A),
+                ("ic", _P), ("n_public", ctypes.c_size_t)]
+
+
+class Groth16Vk(_Handle):
+    """A pa_groth16_vk handle: a verifying key prepared on one device -- e(alpha, beta),
+    -gamma and -delta (affine and prepared), ic[0] and a fixed-base comb table for each of
+    ic[1..l].  `n_public` counts the constant one, `n_inputs` = n_public - 1 is the l of a
+    verify call, `bytes` the device memory held."""
+
+    WHAT = "Groth16 verifying key"
+    FREE = "pa_groth16_vk_free"
+
+    def __init__(self, handle, n_public, nbytes=0, owns=True):
+        super().__init__(handle, owns)
+        self.n_public, self.bytes = int(n_public), int(nbytes)
+        self.n_inputs = self.n_public - 1
+
+    @classmethod
+    def _adopt(cls, handle):
+        """take ownership of a handle pa_groth16_vk_create just returned"""
+        h = ctypes.c_void_p(handle.value)
+        return cls(h, _lib.pa_groth16_vk_n_public(h), _lib.pa_groth16_vk_bytes(h))
+
+    def check_inputs(self, rows, k, stride):
+        """(handle, stride) of a call over k proofs after the checks that need no device: `rows` input rows
+        at `stride` rows per proof (None: n_inputs) must hold the last proof's n_inputs rows"""
+        h = self.handle()
+        l = self.n_inputs
+        stride = l if stride is None else int(stride)
+        k = int(k)
+        if k < 0:
+            raise ValueError("k must not be negative, got %d" % k)
+        if stride < l:
+            raise ValueError("input stride %d is below the key's %d inputs" % (stride, l))
+        need = (k - 1) * stride + l if k and l else 0
+        if rows < need:
+            raise ValueError("%d input rows do not hold %d proofs of %d inputs at stride %d (%d rows)"
+                             % (rows, k, l, stride, need))
+        return h, stride
+
+    def _bytes(self, name, k):
+        k = int(k)
+        if k < 0:
+            raise ValueError("k must not be negative, got %d" % k)
+        n = int(getattr(_lib, name)(self.handle(), k))
+        if n == 0 and k and (name == "pa_groth16_verify_workspace_bytes" or self.n_inputs):
+            raise ValueError("a batch of %d proofs is over PA_GROTH16_VERIFY_MAX_BATCH: split it" % k)
+        return n
+
+    def verify_workspace_bytes(self, k):
+        """pa_groth16_verify_workspace_bytes; a batch over the limit is a ValueError: split it"""
+        return self._bytes("pa_groth16_verify_workspace_bytes", k)
+
+    def input_sum_workspace_bytes(self, k):
+        """pa_groth16_vk_input_sum_workspace_bytes (0 for a key without inputs)"""
+        return self._bytes("pa_groth16_vk_input_sum_workspace_bytes", k)
 
 
 class FrCsr(ctypes.Structure):

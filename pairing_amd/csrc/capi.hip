@@ -19,6 +19,7 @@
 #include "env.h"
 #include "launch.h"
 #include "launch_groth16.h"
+#include "launch_groth16_verify.h"
 #include "launch_msm.h"
 
 namespace {
@@ -2321,6 +2322,334 @@ int pa_groth16_prove(const pa_groth16_pk* pk, const pa_r1cs* r1cs, const pa_fr_n
         return rc;
     PA_TRY(call_sync(), "kernel execution");
     return download(proofs, dout, k * sizeof(pa_groth16_proof));
+}
+
+// ---- Groth16 verifier: the prepared verifying key, and proofs -> valid (kernels_groth16_verify.hip) ----
+struct pa_groth16_vk {
+    int dev = 0;
+    size_t n_public = 0, bytes = 0;
+    // one allocation: e(alpha, beta), -gamma and -delta (affine, next to each other), ic[0], the two
+    // pa_g2_prepared records (-gamma, then -delta), the l comb tables
+    uint64_t* mem = nullptr;
+    const uint64_t *e_ab = nullptr, *neg_gamma = nullptr, *neg_delta = nullptr, *ic0 = nullptr, *prep_gamma = nullptr,
+                   *prep_delta = nullptr, *tables = nullptr;
+    size_t inputs() const { return n_public - 1; }
+};
+
+namespace {
+// Fq one in the ABI's Montgomery words (R mod q)
+constexpr uint64_t kFqOne[6] = {0x760900000002fffdull, 0xebf4000bc40c0002ull, 0x5f48985753c758baull,
+                                0x77ce585370525745ull, 0x5c071a97a256ec6dull, 0x15f65ec3fa80e493ull};
+// -y of an affine G2 record, as CurveAffine::negate (ec.rs:182-187): q - c for each nonzero Fq component
+void g2_affine_negate(pa_g2_affine& p) {
+    static const uint64_t q[6] = {0xb9feffffffffaaabull, 0x1eabfffeb153ffffull, 0x6730d2a0f6b0f624ull,
+                                  0x64774b84f38512bfull, 0x4b1ba7b6434bacd7ull, 0x1a0111ea397fe69aull};
+    if (p.infinity) return;
+    for (pa_fq* c : {&p.y.c0, &p.y.c1}) {
+        uint64_t any = 0;
+        for (uint64_t w : c->l) any |= w;
+        if (!any) continue;
+        uint64_t borrow = 0;
+        for (int i = 0; i < 6; i++) {
+            const uint64_t a = q[i], b = c->l[i];
+            const uint64_t d = a - b - borrow;
+            borrow = (a < b || (a == b && borrow)) ? 1 : 0;
+            c->l[i] = d;
+        }
+    }
+}
+// above this many proofs per call, (acc, -gamma) and (C, -delta) run on the shared-prepared Miller loop; below,
+// all 3 k pairs run through pairing_ml_launch.  Measured (profiles/groth16_verify/default.txt): forced, the shared
+// composition loses at 32768 proofs (three launches of at most one wave per SIMD, one after the other) and wins
+// at 65536; nothing between was measured, so the bound is 65536.  Unlike the regime bounds
+// above, PA_G16V_SHARED_MIN is read at every call, so one process can run both paths (tests, measurements).
+size_t g16v_shared_min() { return pa::env_count("PA_G16V_SHARED_MIN", PA_GROTH16_VERIFY_SHARED_MIN); }
+// the verify call's workspace: the P array (A | acc | C), the Q array (B, then -gamma and -delta k times for the
+// 3 k-pair path), the 3 k Miller values, the k products (the final exponentiation runs in place there when the
+// caller wants no gt), the ok bytes, the input sum's partials and the encoded entry's staging (the three byte
+// arrays and their statuses)
+struct VerifyLayout {
+    size_t p, q, miller, prod, ok, partials, enc_a, enc_b, enc_c, status, bytes;
+};
+VerifyLayout verify_layout(const pa_groth16_vk* vk, size_t k) {
+    VerifyLayout v{};
+    size_t o = 0;
+    v.p = o;        o = align256(o + 3 * k * sizeof(pa_g1_affine));
+    v.q = o;        o = align256(o + 3 * k * sizeof(pa_g2_affine));
+    v.miller = o;   o = align256(o + 3 * k * sizeof(pa_fq12));
+    v.prod = o;     o = align256(o + k * sizeof(pa_fq12));
+    v.ok = o;       o = align256(o + k);
+    v.partials = o; o = align256(o + k * vk->inputs() * sizeof(pa_g1));
+    v.enc_a = o;    o = align256(o + k * 48);
+    v.enc_b = o;    o = align256(o + k * 96);
+    v.enc_c = o;    o = align256(o + k * 48);
+    v.status = o;   o = align256(o + 3 * k);
+    v.bytes = o ? o : 256;
+    return v;
+}
+// what every entry over a key refuses before touching memory; *mont gets the input format
+int vk_call_check(const pa_groth16_vk* vk, const void* inputs, size_t input_stride, unsigned flags, size_t k,
+                  int* mont) {
+    if (!vk) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (flags & ~PA_MSM_SCALARS_MONTGOMERY) return fail(PA_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    if (k > PA_GROTH16_VERIFY_MAX_BATCH)
+        return fail(PA_ERR_INVALID_ARGUMENT, "Groth16 verify batch over PA_GROTH16_VERIFY_MAX_BATCH: split it");
+    if (input_stride < vk->inputs())
+        return fail(PA_ERR_INVALID_ARGUMENT, "input_stride is smaller than the key's n_public - 1 inputs");
+    if (k && vk->inputs() && !inputs) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    *mont = (flags & PA_MSM_SCALARS_MONTGOMERY) ? 1 : 0;
+    return PA_OK;
+}
+int vk_stream_check(const pa_groth16_vk* vk, void* stream) {
+    int dev = 0;
+    PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
+    if (dev != vk->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the Groth16 key");
+    return PA_OK;
+}
+// rows a host caller's input array holds: the last proof's row ends at its l-th input
+size_t input_rows(const pa_groth16_vk* vk, size_t input_stride, size_t k) {
+    return k && vk->inputs() ? (k - 1) * input_stride + vk->inputs() : 0;
+}
+// The chain behind the P and Q arrays (A and C, B in place; dev_status_abc: the decoders' statuses or null):
+// input sum, Miller loops, product of three, final exponentiation, compare.
+int verify_chain(const pa_groth16_vk* vk, const VerifyLayout& v, uint8_t* ws, const uint64_t* inputs,
+                 size_t input_stride, int mont, size_t k, uint8_t* valid, const uint8_t* status_abc,
+                 uint8_t* status_out, pa_fq12* gt, hipStream_t s) {
+    uint64_t *p = (uint64_t*)(ws + v.p), *q = (uint64_t*)(ws + v.q), *ml = (uint64_t*)(ws + v.miller),
+             *prod = (uint64_t*)(ws + v.prod);
+    uint8_t* ok = ws + v.ok;
+    PA_TRY(pa::launch_groth16_input_sum(vk->tables, vk->ic0, inputs, input_stride, mont, vk->inputs(), k,
+                                        (uint64_t*)(ws + v.partials), p + kG1Words * k, s),
+           "kernel launch");
+    if (k < g16v_shared_min()) {
+        PA_TRY(pa::launch_groth16_fill_q(vk->neg_gamma, vk->neg_delta, k, q, s), "kernel launch");
+        PA_TRY(pairing_ml_launch(p, q, ml, 3 * k, s), "kernel launch");
+    } else {
+        // the (A, B) values differ from the reference's Miller values by an Fq2 factor per pair, which the final
+        // exponentiation of the product removes as it does for one pair (pa_pairing_miller_loop_batch_device)
+        PA_TRY(pairing_ml_launch(p, q, ml, k, s), "kernel launch");
+        PA_TRY(pa::launch_miller_loop_shared_gen(p + kG1Words * k, vk->prep_gamma, ml + kF12Words * k, k, s),
+               "kernel launch");
+        PA_TRY(pa::launch_miller_loop_shared_gen(p + kG1Words * 2 * k, vk->prep_delta, ml + kF12Words * 2 * k, k, s),
+               "kernel launch");
+    }
+    PA_TRY(pa::launch_fq12_product3(ml, k, prod, s), "kernel launch");
+    uint64_t* out = gt ? (uint64_t*)gt : prod;
+    PA_TRY(fe_launch(prod, out, ok, k, s), "kernel launch");
+    PA_TRY(pa::launch_groth16_compare(out, ok, vk->e_ab, status_abc, status_out, valid, k, s), "kernel launch");
+    return PA_OK;
+}
+}  // namespace
+
+void pa_groth16_vk_free(pa_groth16_vk* vk) {
+    if (!vk) return;
+    if (vk->mem) (void)hipFree(vk->mem);
+    delete vk;
+}
+
+int pa_groth16_vk_create(const pa_groth16_vkey* key, pa_groth16_vk** out) {
+    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    *out = nullptr;
+    if (!key || !key->ic) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (key->n_public == 0) return fail(PA_ERR_INVALID_ARGUMENT, "n_public counts the constant one: it is at least 1");
+    if (key->n_public - 1 > PA_GROTH16_VK_MAX_INPUTS)
+        return fail(PA_ERR_INVALID_ARGUMENT, "Groth16 verifying keys support n_public - 1 <= PA_GROTH16_VK_MAX_INPUTS");
+    const size_t l = key->n_public - 1, table_words = pa::g1_comb_table_words();
+    // e(alpha, beta) once, with the pairing entry
+    pa_fq12 e_ab;
+    if (int rc = pa_pairing_batch(&key->alpha_g1, &key->beta_g2, &e_ab, 1)) return rc;
+    constexpr size_t kHead = 72 + 2 * kG2Words + kG1Words;
+    uint64_t head[kHead];
+    pa_g2_affine neg[2] = {key->gamma_g2, key->delta_g2};
+    g2_affine_negate(neg[0]);
+    g2_affine_negate(neg[1]);
+    memcpy(head, &e_ab, sizeof e_ab);
+    memcpy(head + 72, neg, sizeof neg);
+    memcpy(head + 72 + 2 * kG2Words, &key->ic[0], sizeof(pa_g1_affine));
+    // only the flag byte of a record's last word is defined
+    for (size_t w : {72 + kG2Words - 1, 72 + 2 * kG2Words - 1, kHead - 1}) head[w] &= 0xff;
+    // ic[1..l] as the Jacobian records the table builder reads
+    std::vector<pa_g1> bases(l);
+    for (size_t i = 0; i < l; i++) {
+        const pa_g1_affine& a = key->ic[i + 1];
+        memset(&bases[i], 0, sizeof(pa_g1));
+        if (a.infinity) {
+            memcpy(bases[i].y.l, kFqOne, sizeof kFqOne);
+        } else {
+            bases[i].x = a.x;
+            bases[i].y = a.y;
+            memcpy(bases[i].z.l, kFqOne, sizeof kFqOne);
+        }
+    }
+    const size_t prep_at = align256(kHead * 8), tables_at = align256(prep_at + 2 * sizeof(pa_g2_prepared));
+    pa_groth16_vk* vk = new pa_groth16_vk;
+    vk->n_public = key->n_public;
+    vk->bytes = tables_at + l * table_words * 8;
+    int rc = PA_OK;
+    DevBuf dbases, dws;
+    hipError_t e = hipGetDevice(&vk->dev);
+    if (e == hipSuccess) e = hipMalloc((void**)&vk->mem, vk->bytes);
+    if (e != hipSuccess) rc = fail(hip_code(e), "create Groth16 verifying key", e);
+    if (!rc) rc = upload(dbases, bases.data(), l * sizeof(pa_g1));
+    if (!rc && (e = dws.alloc(pa::g1_comb_workspace_words() * 8)) != hipSuccess)
+        rc = fail(hip_code(e), "device scratch", e);
+    if (!rc) {
+        uint8_t* m = (uint8_t*)vk->mem;
+        vk->e_ab = vk->mem;
+        vk->neg_gamma = vk->mem + 72;
+        vk->neg_delta = vk->neg_gamma + kG2Words;
+        vk->ic0 = vk->neg_delta + kG2Words;
+        vk->prep_gamma = (const uint64_t*)(m + prep_at);
+        vk->prep_delta = (const uint64_t*)(m + prep_at + sizeof(pa_g2_prepared));
+        vk->tables = (const uint64_t*)(m + tables_at);
+        const hipStream_t s = call_stream();
+        e = hipMemcpyAsync(vk->mem, head, sizeof head, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = pa::launch_g2_prepare(vk->neg_gamma, (uint64_t*)(m + prep_at), 2, s);
+        // one table per base, the builder's scratch reused in stream order
+        for (size_t i = 0; i < l && e == hipSuccess; i++)
+            e = pa::launch_g1_comb_table(dbases.as<uint64_t>() + 18 * i, (uint64_t*)(m + tables_at) + table_words * i,
+                                         dws.as<uint64_t>(), s);
+        if (e == hipSuccess) e = call_sync();   // `head` and the scratch go out of scope
+        if (e != hipSuccess) rc = fail(hip_code(e), "create Groth16 verifying key", e);
+    }
+    if (rc) {
+        pa_groth16_vk_free(vk);
+        return rc;
+    }
+    *out = vk;
+    return PA_OK;
+}
+size_t pa_groth16_vk_n_public(const pa_groth16_vk* vk) { return vk ? vk->n_public : 0; }
+size_t pa_groth16_vk_bytes(const pa_groth16_vk* vk) { return vk ? vk->bytes : 0; }
+
+size_t pa_groth16_vk_input_sum_workspace_bytes(const pa_groth16_vk* vk, size_t k) {
+    return vk && k <= PA_GROTH16_VERIFY_MAX_BATCH ? k * vk->inputs() * sizeof(pa_g1) : 0;
+}
+
+int pa_groth16_vk_input_sum_device(const pa_groth16_vk* vk, const pa_fr* inputs, size_t input_stride, unsigned flags,
+                                   size_t k, pa_g1_affine* out, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    int mont = 0;
+    if (int rc = vk_call_check(vk, inputs, input_stride, flags, k, &mont)) return rc;
+    if (k == 0) return PA_OK;
+    const size_t need = pa_groth16_vk_input_sum_workspace_bytes(vk, k);
+    if (!out || (need && !workspace)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (workspace_bytes < need)
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_groth16_vk_input_sum_workspace_bytes");
+    if (int rc = vk_stream_check(vk, stream)) return rc;
+    PA_TRY(pa::launch_groth16_input_sum(vk->tables, vk->ic0, (const uint64_t*)inputs, input_stride, mont, vk->inputs(),
+                                        k, (uint64_t*)workspace, (uint64_t*)out, (hipStream_t)stream),
+           "kernel launch");
+    return PA_OK;
+}
+
+int pa_groth16_vk_input_sum(const pa_groth16_vk* vk, const pa_fr* inputs, size_t input_stride, unsigned flags, size_t k,
+                            pa_g1_affine* out) {
+    int mont = 0;
+    if (int rc = vk_call_check(vk, inputs, input_stride, flags, k, &mont)) return rc;
+    if (k == 0) return PA_OK;
+    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    DevBuf din, dout, dws;
+    int rc;
+    if ((rc = upload(din, inputs, input_rows(vk, input_stride, k) * sizeof(pa_fr)))) return rc;
+    PA_TRY(dout.alloc(k * sizeof(pa_g1_affine)), "device scratch");
+    const size_t ws = pa_groth16_vk_input_sum_workspace_bytes(vk, k);
+    PA_TRY(dws.alloc(ws), "device scratch");
+    if ((rc = pa_groth16_vk_input_sum_device(vk, din.as<pa_fr>(), input_stride, flags, k, dout.as<pa_g1_affine>(),
+                                             dws.p, ws, call_stream())))
+        return rc;
+    return download(out, dout, k * sizeof(pa_g1_affine));
+}
+
+size_t pa_groth16_verify_workspace_bytes(const pa_groth16_vk* vk, size_t k) {
+    return vk && k <= PA_GROTH16_VERIFY_MAX_BATCH ? verify_layout(vk, k).bytes : 0;
+}
+
+int pa_groth16_verify_device(const pa_groth16_vk* vk, const pa_groth16_proof* proofs, const pa_fr* inputs,
+                             size_t input_stride, unsigned flags, size_t k, uint8_t* valid, pa_fq12* gt,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    int mont = 0;
+    if (int rc = vk_call_check(vk, inputs, input_stride, flags, k, &mont)) return rc;
+    if (k == 0) return PA_OK;
+    if (!proofs || !valid || !workspace) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    const VerifyLayout v = verify_layout(vk, k);
+    if (workspace_bytes < v.bytes)
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_groth16_verify_workspace_bytes");
+    if (int rc = vk_stream_check(vk, stream)) return rc;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    const hipStream_t s = (hipStream_t)stream;
+    PA_TRY(pa::launch_groth16_split((const uint64_t*)proofs, k, (uint64_t*)(ws + v.p), (uint64_t*)(ws + v.q), s),
+           "kernel launch");
+    return verify_chain(vk, v, ws, (const uint64_t*)inputs, input_stride, mont, k, valid, nullptr, nullptr, gt, s);
+}
+
+int pa_groth16_verify_encoded_device(const pa_groth16_vk* vk, const uint8_t* enc, const pa_fr* inputs,
+                                     size_t input_stride, unsigned flags, size_t k, uint8_t* valid, uint8_t* status,
+                                     pa_fq12* gt, void* workspace, size_t workspace_bytes, void* stream) {
+    int mont = 0;
+    if (int rc = vk_call_check(vk, inputs, input_stride, flags, k, &mont)) return rc;
+    if (k == 0) return PA_OK;
+    if (!enc || !valid || !status || !workspace) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    const VerifyLayout v = verify_layout(vk, k);
+    if (workspace_bytes < v.bytes)
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_groth16_verify_workspace_bytes");
+    if (int rc = vk_stream_check(vk, stream)) return rc;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    const hipStream_t s = (hipStream_t)stream;
+    uint64_t *p = (uint64_t*)(ws + v.p), *q = (uint64_t*)(ws + v.q);
+    uint8_t* st = ws + v.status;
+    PA_TRY(pa::launch_groth16_gather(enc, k, ws + v.enc_a, ws + v.enc_b, ws + v.enc_c, s), "kernel launch");
+    // the checked decoders write the P and Q arrays themselves (the point at infinity for a record that fails)
+    PA_TRY(pa::launch_decode(1, 1, 1, ws + v.enc_a, k, p, st, s), "kernel launch");
+    PA_TRY(pa::launch_decode(2, 1, 1, ws + v.enc_b, k, q, st + k, s), "kernel launch");
+    PA_TRY(pa::launch_decode(1, 1, 1, ws + v.enc_c, k, p + kG1Words * 2 * k, st + 2 * k, s), "kernel launch");
+    return verify_chain(vk, v, ws, (const uint64_t*)inputs, input_stride, mont, k, valid, st, status, gt, s);
+}
+
+namespace {
+// both host entries: one stream round trip, like pa_multi_pairing_batch
+int verify_host(const pa_groth16_vk* vk, const pa_groth16_proof* proofs, const uint8_t* enc, const pa_fr* inputs,
+                size_t input_stride, unsigned flags, size_t k, uint8_t* valid, uint8_t* status, pa_fq12* gt) {
+    int mont = 0;
+    if (int rc = vk_call_check(vk, inputs, input_stride, flags, k, &mont)) return rc;
+    if (k == 0) return PA_OK;
+    if ((!proofs && !enc) || !valid || (enc && !status)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    DevBuf dproofs, din, dflags, dgt, dws;
+    int rc;
+    if ((rc = enc ? upload(dproofs, enc, k * PA_GROTH16_ENCODED_PROOF_BYTES)
+                  : upload(dproofs, proofs, k * sizeof(pa_groth16_proof))))
+        return rc;
+    if ((rc = upload(din, inputs, input_rows(vk, input_stride, k) * sizeof(pa_fr)))) return rc;
+    PA_TRY(dflags.alloc(4 * k), "device scratch");   // valid, then the 3 k statuses
+    if (gt) PA_TRY(dgt.alloc(k * sizeof(pa_fq12)), "device scratch");
+    const size_t ws = verify_layout(vk, k).bytes;
+    PA_TRY(dws.alloc(ws), "device scratch");
+    const hipStream_t s = call_stream();
+    uint8_t* dvalid = dflags.as<uint8_t>();
+    pa_fq12* dg = gt ? dgt.as<pa_fq12>() : nullptr;
+    rc = enc ? pa_groth16_verify_encoded_device(vk, dproofs.as<uint8_t>(), din.as<pa_fr>(), input_stride, flags, k,
+                                                dvalid, dvalid + k, dg, dws.p, ws, s)
+             : pa_groth16_verify_device(vk, dproofs.as<pa_groth16_proof>(), din.as<pa_fr>(), input_stride, flags, k,
+                                        dvalid, dg, dws.p, ws, s);
+    if (rc) return rc;
+    PA_TRY(hipMemcpyAsync(valid, dvalid, k, hipMemcpyDeviceToHost, s), "D2H copy");
+    if (enc) PA_TRY(hipMemcpyAsync(status, dvalid + k, 3 * k, hipMemcpyDeviceToHost, s), "D2H copy");
+    if (gt) PA_TRY(hipMemcpyAsync(gt, dgt.p, k * sizeof(pa_fq12), hipMemcpyDeviceToHost, s), "D2H copy");
+    PA_TRY(hipStreamSynchronize(s), "kernel execution");
+    return PA_OK;
+}
+}  // namespace
+
+int pa_groth16_verify(const pa_groth16_vk* vk, const pa_groth16_proof* proofs, const pa_fr* inputs, size_t input_stride,
+                      unsigned flags, size_t k, uint8_t* valid, pa_fq12* gt) {
+    if (k && !proofs) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    return verify_host(vk, proofs, nullptr, inputs, input_stride, flags, k, valid, nullptr, gt);
+}
+
+int pa_groth16_verify_encoded(const pa_groth16_vk* vk, const uint8_t* enc, const pa_fr* inputs, size_t input_stride,
+                              unsigned flags, size_t k, uint8_t* valid, uint8_t* status, pa_fq12* gt) {
+    if (k && !enc) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    return verify_host(vk, nullptr, enc, inputs, input_stride, flags, k, valid, status, gt);
 }
 
 // ---- CurveProjective / CurveAffine surface, G1 and G2 (kernels_group.hip) ----

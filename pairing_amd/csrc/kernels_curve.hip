@@ -20,6 +20,7 @@
 // are left bit-for-bit untouched, as in the reference (ec.rs:255-257, 271, 285).
 #include <mutex>
 
+#include "comb.h"
 #include "curve_fl.h"
 #include "dec_quad.h"
 #include "glv_split.h"
@@ -28,11 +29,6 @@
 
 namespace pa {
 
-constexpr int kCombWindows = 33;      // 8-bit digits of a 255-bit scalar + final carry
-constexpr int kCombEntries = 128;     // |d| in 1..128
-constexpr int kG1Jac = 18;            // u64 words per Jacobian G1
-constexpr uint32_t kFlInfinity = 0xffffffffu;  // table entry marker: no lazy limb has all 32 bits set
-constexpr int kFlPair = 14;           // u64 words per table entry: x, y as 14 x 28-bit limbs (lazy core)
 constexpr int kNormChunk = 8;         // points per lane in batch_normalization (4 measured slower at 2^18)
 // GLV (endomorphism) form of the comb, used when the base passes the G1
 // membership test phi(P) == -[x^2] P (Scott, eprint 2021/1130; the decode
@@ -44,9 +40,6 @@ constexpr int kNormChunk = 8;         // points per lane in batch_normalization 
 // A base outside G1 (or off the curve) takes a 256-bit double-and-add ladder
 // (k_g1_fixed_base_ladder); both paths are launched, each kernel reading the
 // membership flag and returning at once when it is not its path's.
-constexpr int kGlvWindows = 17;
-constexpr int kTableRows = 2 * kGlvWindows;   // >= kCombWindows
-static_assert(kTableRows >= kCombWindows, "table rows");
 // beta (a primitive cube root of unity in Fq, Montgomery R = 2^384), the decode kernel's kBeta
 __constant__ const uint64_t kGlvBeta[6] = {0x30f1361b798a64e8ULL, 0xf3b8ddab7ece5a2aULL, 0x16a8ca3ac61577f7ULL,
                                            0xc26a2ff874fd029bULL, 0x3636b76660701c6eULL, 0x051ba4ab241b6160ULL};
@@ -334,26 +327,6 @@ PA_DEV int glv_digit(const uint64_t v[3], int win, int& carry) {
     carry = d > 128 ? 1 : 0;
     if (d > 128) d -= 256;
     return d;
-}
-
-PA_DEV void comb_add_entry(FlJac& acc, bool& untouched, bool& changed, const uint64_t* table_fl, int row, int d,
-                           bool flip) {
-    const int ad = d < 0 ? -d : d;
-    const uint2* src = reinterpret_cast<const uint2*>(table_fl + (size_t)kFlPair * (row * kCombEntries + ad - 1));
-    F<1> tx, ty;
-#pragma unroll
-    for (int k = 0; k < 7; k++) {
-        const uint2 a = src[k], b = src[7 + k];
-        tx.w[2 * k] = a.x;
-        tx.w[2 * k + 1] = a.y;
-        ty.w[2 * k] = b.x;
-        ty.w[2 * k + 1] = b.y;
-    }
-    if (tx.w[0] != kFlInfinity) {  // adding the identity is add_assign_mixed's no-op
-        const F<2> oy = ((d < 0) != flip) ? neg(ty) : relax<2>(ty);
-        fl_jac_add_mixed(acc, untouched, tx, oy);
-        changed = true;
-    }
 }
 
 // GLV comb multiply, windows [w0, w1) of both halves: s g = rem g + q psi(g)

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, W_PROOF, FrNttDomain, G1MsmBases, G2MsmBases, Groth16Pk, R1cs, _lib, call, csr_offsets, msm_bases, msm_scalars, ntt_mode
+from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, W_PROOF, FrNttDomain, G1MsmBases, G2MsmBases, Groth16Pk, Groth16Vk, R1cs, _lib, call, csr_offsets, msm_bases, msm_scalars, ntt_mode
 
 
 def _stream_ptr(stream):
@@ -419,6 +419,80 @@ def groth16_prove(pk, system, domain, witness, r, s, out, workspace, stream=None
     args = (_dptr(witness, 4, "witness"), _dptr(r, 4, "r"), _dptr(s, 4, "s"))
     call("pa_groth16_prove_device", h, hr, hd, *args, k, _dptr(out, W_PROOF, "out"),
          ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
+
+
+def groth16_verify_workspace(vk, k, device):
+    """A device workspace sized for groth16_verify or groth16_verify_encoded over k proofs
+    (pa_groth16_verify_workspace_bytes)."""
+    if not isinstance(vk, Groth16Vk):
+        raise ValueError("vk must come from groth16_vk")
+    return torch.empty(vk.verify_workspace_bytes(k), dtype=torch.uint8, device=device)
+
+
+def _verify_args(vk, k, inputs, stride, montgomery, valid, gt, workspace):
+    """the arguments both verify entries share, after the checks that need no device"""
+    if not isinstance(vk, Groth16Vk):
+        raise ValueError("vk must come from groth16_vk")
+    vk.handle()   # a closed object is rejected first
+    flag = msm_scalars(montgomery)
+    h, stride = vk.check_inputs(inputs.shape[0] if inputs is not None else 0, k, stride)
+    if gt is not None:
+        _rows(gt, k, "gt")
+    if valid.numel() < k:
+        raise ValueError("valid has %d elements, the call needs %d" % (valid.numel(), k))
+    need = vk.verify_workspace_bytes(k)
+    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.dtype != torch.uint8 \
+            or workspace.numel() < need:
+        raise ValueError("workspace must be a contiguous uint8 CUDA tensor of >= %d bytes" % need)
+    x = _dptr(inputs, 4, "inputs") if vk.n_inputs and k else ctypes.c_void_p(0)
+    g = _dptr(gt, W_FQ12, "gt") if gt is not None else ctypes.c_void_p(0)
+    return h, x, stride, flag, _flags(valid, k, "valid"), g, ctypes.c_void_p(workspace.data_ptr()), workspace.numel()
+
+
+def groth16_verify(vk, proofs, inputs, valid, workspace, gt=None, stride=None, montgomery=True, stream=None):
+    """k = proofs.shape[0] Groth16 proofs checked in HBM (pa_groth16_verify_device): proofs (k, 51)
+    int64 as groth16_prove writes them; inputs (rows, 4) int64, row i of proof j at j * stride + i
+    (stride None: n_inputs rows per proof; a view `witness[1:]` with stride = n_vars reads the
+    prover's witness buffer as it lies), Montgomery Fr or (montgomery=False) FrRepr; valid (k,)
+    uint8; gt None or (k, 72) int64; workspace from groth16_verify_workspace.  Everything is
+    enqueued on the stream; nothing is allocated, synchronized or read back."""
+    k = proofs.shape[0]
+    h, x, stride, flag, v, g, ws, ws_bytes = _verify_args(vk, k, inputs, stride, montgomery, valid, gt, workspace)
+    call("pa_groth16_verify_device", h, _dptr(proofs, W_PROOF, "proofs"), x, stride, flag, k, v, g, ws, ws_bytes,
+         _stream_ptr(stream))
+
+
+def groth16_verify_encoded(vk, data, inputs, valid, status, workspace, gt=None, stride=None, montgomery=True,
+                           stream=None):
+    """groth16_verify for k = data.shape[0] proofs off the wire (pa_groth16_verify_encoded_device):
+    data (k, 192) uint8, A, B and C compressed; status (k, 3) uint8 gets the decoders' codes.  A
+    proof with a nonzero status is not valid and its gt is meaningless."""
+    if not data.is_cuda or not data.is_contiguous() or data.dtype != torch.uint8 or data.dim() != 2 \
+            or data.shape[1] != 192:
+        raise ValueError("data must be a contiguous (k, 192) uint8 CUDA tensor")
+    k = data.shape[0]
+    h, x, stride, flag, v, g, ws, ws_bytes = _verify_args(vk, k, inputs, stride, montgomery, valid, gt, workspace)
+    call("pa_groth16_verify_encoded_device", h, ctypes.c_void_p(data.data_ptr()), x, stride, flag, k, v,
+         _flags(status, 3 * k, "status"), g, ws, ws_bytes, _stream_ptr(stream))
+
+
+def groth16_input_sum(vk, inputs, k, out, workspace=None, stride=None, montgomery=True, stream=None):
+    """The public-input sums of k proofs into the first k rows of `out` ((rows, 13) int64 affine
+    records; pa_groth16_vk_input_sum_device).  workspace: a uint8 buffer of
+    vk.input_sum_workspace_bytes(k), not needed for a key without inputs."""
+    if not isinstance(vk, Groth16Vk):
+        raise ValueError("vk must come from groth16_vk")
+    vk.handle()   # a closed object is rejected first
+    flag = msm_scalars(montgomery)
+    h, stride = vk.check_inputs(inputs.shape[0] if inputs is not None else 0, k, stride)
+    _rows(out, k, "out")
+    need = vk.input_sum_workspace_bytes(k)
+    if need and (workspace is None or not workspace.is_cuda or not workspace.is_contiguous()
+                 or workspace.dtype != torch.uint8 or workspace.numel() < need):
+        raise ValueError("workspace must be a contiguous uint8 CUDA tensor of >= %d bytes" % need)
+    x = _dptr(inputs, 4, "inputs") if vk.n_inputs and k else ctypes.c_void_p(0)
+    call("pa_groth16_vk_input_sum_device", h, x, stride, flag, int(k), _dptr(out, W_G1A, "out"),
+         ctypes.c_void_p(workspace.data_ptr()) if need else ctypes.c_void_p(0), need, _stream_ptr(stream))
 
 
 def multiexp_workspace(group, n, device):
