@@ -705,10 +705,11 @@ int pa_groth16_prove(const pa_groth16_pk *pk, const pa_r1cs *r1cs, const pa_fr_n
  * PA_ERR_INVALID_ARGUMENT.  Creation waits for the tables.  alpha, beta, gamma
  * and delta are taken as they are (no curve or subgroup test).  ic points may
  * be the point at infinity, and may lie on the curve outside G1: the comb
- * assumes no subgroup, and the sum is the reference's as long as no ic point
- * has an order below 129 (the table holds d ic[i] for d <= 128; E(Fq) has such
- * points, of order 3, 11, 33 and 121, none of them in G1).  ic points off the
- * curve are undefined.  The object may be used from any host thread and lives
+ * assumes no subgroup and no order.  The table holds d ic[i] for d <= 128;
+ * for an ic point of order below 129 (E(Fq) has such points, of order 3, 11,
+ * 33 and 121, none of them in G1) some of these are the identity, which the
+ * table marks and the sum skips, so the sum is the reference's for them too.
+ * ic points off the curve are undefined.  The object may be used from any host thread and lives
  * until pa_groth16_vk_free (NULL is a no-op); work that reads it must have
  * completed before it is freed.
  *
@@ -803,7 +804,10 @@ int pa_g1_batch_normalization_device(pa_g1 *v, size_t n, void *stream);
 /* u64 words of the fixed-base table and of the scratch used to build it.  The
  * multiply stages below give the reference's wNAF point for the window
  * recommended_wnaf_for_num_scalars(n) (its add_nocarry wrap included, see
- * pa_g1_wnaf_fixed_base). */
+ * pa_g1_wnaf_fixed_base).  The fixed-base entries and the Groth16 verifying
+ * key (pa_groth16_vk_create's ic) take any on-curve point, of any order: a
+ * table row d * B that is the identity (a base of order 3, 11, 33, ...) is
+ * marked and skipped like a zero base's. */
 size_t pa_g1_fixed_base_table_words(void);
 size_t pa_g1_fixed_base_workspace_words(void);
 int pa_g1_fixed_base_table_device(const pa_g1 *base, uint64_t *table, uint64_t *workspace, void *stream);

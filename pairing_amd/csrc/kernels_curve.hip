@@ -134,7 +134,11 @@ __global__ void __launch_bounds__(64) k_g1_comb_entries(const uint64_t* __restri
         }
         return;
     }
-    // from d's top bit (d < 2^8 < the order: no intermediate is zero)
+    // from d's top bit.  A base of small order m (E(Fq) has points of order 3,
+    // 11, 33, ...) passes through zero wherever m divides a prefix of d: the
+    // doubling keeps z == 0 (z3 = 2 y z) and fl_jac_add restarts from b, so
+    // acc.z ends at zero exactly when m | d.  Such a row is the identity and
+    // gets the zero base's mark.
     const FlJac b = {fl_from_abi(b0.x), fl_from_abi(b0.y), fl_from_abi(b0.z)};
     FlJac acc = b;
     const int top = 31 - __builtin_clz(d);
@@ -143,8 +147,17 @@ __global__ void __launch_bounds__(64) k_g1_comb_entries(const uint64_t* __restri
         fl_jac_double(acc);
         if ((d >> bit) & 1) fl_jac_add(acc, b);
     }
+    const Fq az = fl_to_abi(acc.z);
+    if (fq_is_zero(az)) {
+#pragma unroll
+        for (int k = 0; k < 28; k++) {
+            o[k] = kFlInfinity;
+            if (phi_rows) op[k] = kFlInfinity;
+        }
+        return;
+    }
     Fq zi;
-    fq_inv(zi, fl_to_abi(acc.z));
+    fq_inv(zi, az);
     const F<1> zf = fl_from_abi(zi);
     const F<1> zz = sqr(zf);
     const F<1> x = mul(acc.x, zz);
