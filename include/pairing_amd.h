@@ -699,8 +699,9 @@ int pa_groth16_prove(const pa_groth16_pk *pk, const pa_r1cs *r1cs, const pa_fr_n
  * The key object lives on the device that was current at creation.  It holds
  * e(alpha, beta), -gamma and -delta as affine and as pa_g2_prepared records,
  * ic[0], and for each of ic[1..l] one fixed-base comb table
- * (pa_g1_fixed_base_table_words() u64, about 0.49 MB; exact digits).  l is at
- * most PA_GROTH16_VK_MAX_INPUTS (the tables then take 250 MB); creation above
+ * (pa_g1_fixed_base_table_words() u64, about 0.49 MB; exact digits), and for
+ * the aggregate check below two more tables (ic[0], alpha) and -beta.  l is at
+ * most PA_GROTH16_VK_MAX_INPUTS (the l + 2 tables then take 251 MB); creation above
  * it, with n_public == 0 or with a NULL pointer returns
  * PA_ERR_INVALID_ARGUMENT.  Creation waits for the tables.  alpha, beta, gamma
  * and delta are taken as they are (no curve or subgroup test).  ic points may
@@ -792,6 +793,99 @@ int pa_groth16_verify_encoded_device(const pa_groth16_vk *vk, const uint8_t *dev
 int pa_groth16_verify_encoded(const pa_groth16_vk *vk, const uint8_t *enc, const pa_fr *inputs, size_t input_stride,
                               unsigned flags, size_t k, uint8_t *valid, uint8_t *status,
                               pa_fq12 *gt);   /* host memory */
+
+/* ---- Groth16 aggregate check: k proofs in one randomised pairing product ----
+ * bellman's verify_proofs_batch over a pa_groth16_vk.  With weights z_j (any
+ * 128-bit integers; draw them from a cryptographic generator, fresh per call
+ * and unknown to whoever made the proofs):
+ *   s_0     = sum_j z_j mod r,   s_{i+1} = sum_j z_j x_{j,i} mod r   (i < l)
+ *   A'_j    = into_affine(z_j A_j)
+ *   accS    = into_affine(s_0 ic[0] + sum_i s_{i+1} ic[i+1])
+ *   CS      = into_affine(sum_j z_j C_j)
+ *   alphaS  = into_affine(s_0 alpha)
+ *   gt      = final_exponentiation(prod_j ML(A'_j, B_j) ML(accS, -gamma)
+ *                                  ML(CS, -delta) ML(alphaS, -beta))
+ *   valid   = (the final exponentiation is not None) && gt == Fq12::one
+ * k + 3 Miller loops (one launch) and one final exponentiation, against 3 k
+ * and k of pa_groth16_verify.  One verdict for the batch: when it is 0, run
+ * pa_groth16_verify on the same proofs to find the bad ones.  The two entries
+ * compute different things, so neither falls back to the other.  Measured on
+ * one MI355X (profiles/groth16_verify_aggregate/, l = 4): up to 2^10 proofs
+ * pa_groth16_verify_device is the faster call (k = 1: 2.4 ms against 4.6;
+ * 2^10: 5.6 against 7.5 -- the G1 side costs 3 to 4.6 ms at any k), at 2^14
+ * and above this one is (2^14: 10.2 ms against 12.3, 15.9 at l = 32; 2^16:
+ * 19.6 against 29.1); nothing between 2^10 and 2^14 was measured.
+ *
+ * When every A_j and C_j is in G1 and every B_j in G2, bilinearity gives
+ * gt = prod_j (gt_j / e(alpha, beta))^z_j with gt_j of pa_groth16_verify: all
+ * proofs valid gives one, and a batch with an invalid proof gives one with
+ * probability about 2^-128 over random z.  Both statements need subgroup
+ * membership.  pa_groth16_verify_aggregate and _points take the points as they
+ * are, like every records entry; pa_groth16_verify_aggregate_encoded enforces
+ * membership through the checked decoders.  z_j = 0 drops proof j from the
+ * check.  No scalar multiplication here uses the endomorphism: z P and the
+ * sums are the group law of E(Fq), well defined for any on-curve point, points
+ * of small order included; points off the curve are undefined.  FrRepr inputs
+ * are taken mod r; a Montgomery row not below r is undefined.
+ *
+ * z: k rows of two u64, little-endian (on the device 16-byte aligned, like
+ * the scalars of pa_g1_multiexp_u128_device: a pointer that is not is
+ * refused with PA_ERR_INVALID_ARGUMENT).  valid: one byte.  gt: one pa_fq12 or
+ * NULL; where the final exponentiation is None it is zeroed and valid = 0.
+ * _encoded: records and statuses as pa_groth16_verify_encoded (3 k status
+ * bytes, per proof); any nonzero status forces valid = 0.  _points: the P
+ * array alone, k + 3 affine records A'_0 .. A'_{k-1} | accS | CS | alphaS.
+ * k = 0: valid = 1, gt = one, nothing else is launched or written (_points
+ * writes three points at infinity).
+ *
+ * pa_groth16_vk_create builds for these entries two more comb tables (ic[0]
+ * and alpha, any on-curve point) and the affine -beta; pa_groth16_vk_bytes
+ * counts them.  The device entries follow pa_groth16_verify_device: device
+ * pointers, everything on `stream` (the MSM orders its side streams with
+ * events), no allocation, no staging, no synchronisation, the same errors
+ * (PA_ERR_INVALID_ARGUMENT before anything runs).  workspace:
+ * pa_groth16_verify_aggregate_workspace_bytes(vk, k) bytes for all three
+ * (never 0 for a key, also at k = 0; monotone in k; 0 for a NULL key or k
+ * above PA_GROTH16_VERIFY_MAX_BATCH).  It begins with the P array and, at the
+ * next multiple of 256 bytes, the Q array (k + 3 pa_g2_affine: B_0 .. |
+ * -gamma | -delta | -beta).
+ *
+ * pa_g1_multiexp_u128*: sum_i s_i P_i for 128-bit scalars (rows of two u64,
+ * little-endian) over per-call bases, a Jacobian record: the same point as
+ * pa_g1_multiexp over the zero-extended scalars, for any on-curve bases (no
+ * endomorphism, no membership assumption), in ceil(130 / c) windows instead of
+ * ceil(257 / c).  n < 2^31; n = 0 gives zero.
+ * pa_g1_multiexp_u128_workspace_bytes(n) is the largest plan of any n' <= n,
+ * so it never decreases with n (the plan of one n does: fewer windows after a
+ * width change, a shorter continuation array after a chunk step) and a
+ * workspace sized for the largest call serves every smaller one. */
+size_t pa_g1_multiexp_u128_workspace_bytes(size_t n);
+int pa_g1_multiexp_u128_device(const pa_g1_affine *dev_bases, const uint64_t *dev_scalars, size_t n, pa_g1 *dev_out,
+                               void *workspace, size_t workspace_bytes, void *stream);
+int pa_g1_multiexp_u128(const pa_g1_affine *bases, const uint64_t *scalars, size_t n, pa_g1 *out);   /* host memory */
+size_t pa_groth16_verify_aggregate_workspace_bytes(const pa_groth16_vk *vk, size_t k);
+int pa_groth16_verify_aggregate_device(const pa_groth16_vk *vk, const pa_groth16_proof *dev_proofs,
+                                       const pa_fr *dev_inputs, size_t input_stride, unsigned flags,
+                                       const uint64_t *dev_z, size_t k, uint8_t *dev_valid, pa_fq12 *dev_gt,
+                                       void *workspace, size_t workspace_bytes, void *stream);
+int pa_groth16_verify_aggregate(const pa_groth16_vk *vk, const pa_groth16_proof *proofs, const pa_fr *inputs,
+                                size_t input_stride, unsigned flags, const uint64_t *z, size_t k, uint8_t *valid,
+                                pa_fq12 *gt);   /* host memory */
+int pa_groth16_verify_aggregate_encoded_device(const pa_groth16_vk *vk, const uint8_t *dev_enc,
+                                               const pa_fr *dev_inputs, size_t input_stride, unsigned flags,
+                                               const uint64_t *dev_z, size_t k, uint8_t *dev_valid,
+                                               uint8_t *dev_status, pa_fq12 *dev_gt, void *workspace,
+                                               size_t workspace_bytes, void *stream);
+int pa_groth16_verify_aggregate_encoded(const pa_groth16_vk *vk, const uint8_t *enc, const pa_fr *inputs,
+                                        size_t input_stride, unsigned flags, const uint64_t *z, size_t k,
+                                        uint8_t *valid, uint8_t *status, pa_fq12 *gt);   /* host memory */
+int pa_groth16_verify_aggregate_points_device(const pa_groth16_vk *vk, const pa_groth16_proof *dev_proofs,
+                                              const pa_fr *dev_inputs, size_t input_stride, unsigned flags,
+                                              const uint64_t *dev_z, size_t k, pa_g1_affine *dev_out,
+                                              void *workspace, size_t workspace_bytes, void *stream);
+int pa_groth16_verify_aggregate_points(const pa_groth16_vk *vk, const pa_groth16_proof *proofs, const pa_fr *inputs,
+                                       size_t input_stride, unsigned flags, const uint64_t *z, size_t k,
+                                       pa_g1_affine *out);   /* host memory */
 
 /* ---- device-resident variants (pointers are device memory) ---- */
 int pa_g1_decode_batch_device(const uint8_t *enc, size_t n, int compressed, int checked, pa_g1_affine *out,

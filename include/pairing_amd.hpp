@@ -883,15 +883,75 @@ public:
         return out;
     }
 
+    // The aggregate check (pa_groth16_verify_aggregate): all k proofs in one randomised pairing product, one
+    // verdict for the batch.  z: the k 128-bit weights, two little-endian words each, drawn by the caller from a
+    // cryptographic generator.  When the batch fails, verify() finds the bad proofs; for small batches verify()
+    // is also the faster call (README.md).  gt (optional) gets the one pairing-product value, one when valid.
+    bool verify_aggregate(const std::vector<pa_groth16_proof>& proofs, const std::vector<pa_fr>& inputs,
+                          const std::vector<uint64_t>& z, size_t k, bool montgomery = true,
+                          pa_fq12* gt = nullptr) const {
+        if (proofs.size() != k) throw std::invalid_argument("Groth16Verifier::verify_aggregate: proofs are not k records");
+        weighted(inputs, z, k, "Groth16Verifier::verify_aggregate");
+        uint8_t valid = 0;
+        check(pa_groth16_verify_aggregate(vk_, proofs.data(), inputs.data(), n_inputs(), flags(montgomery), z.data(), k,
+                                          &valid, gt),
+              "Groth16Verifier::verify_aggregate");
+        return valid != 0;
+    }
+    struct AggregateEncodedResult {   // status: as EncodedResult's; any nonzero code makes the batch not valid
+        bool valid;
+        std::vector<uint8_t> status;
+    };
+    AggregateEncodedResult verify_aggregate_encoded(const std::vector<uint8_t>& bytes, const std::vector<pa_fr>& inputs,
+                                                    const std::vector<uint64_t>& z, size_t k, bool montgomery = true,
+                                                    pa_fq12* gt = nullptr) const {
+        if (bytes.size() != k * PA_GROTH16_ENCODED_PROOF_BYTES)
+            throw std::invalid_argument("Groth16Verifier::verify_aggregate_encoded: bytes are not k records of 192");
+        weighted(inputs, z, k, "Groth16Verifier::verify_aggregate_encoded");
+        AggregateEncodedResult r{false, std::vector<uint8_t>(3 * k)};
+        uint8_t valid = 0;
+        check(pa_groth16_verify_aggregate_encoded(vk_, bytes.data(), inputs.data(), n_inputs(), flags(montgomery),
+                                                  z.data(), k, &valid, r.status.data(), gt),
+              "Groth16Verifier::verify_aggregate_encoded");
+        r.valid = valid != 0;
+        return r;
+    }
+    // the G1 side of the aggregate check: z_j A_j (k records) | the weighted input sum | sum_j z_j C_j | s_0 alpha
+    std::vector<pa_g1_affine> aggregate_points(const std::vector<pa_groth16_proof>& proofs,
+                                               const std::vector<pa_fr>& inputs, const std::vector<uint64_t>& z,
+                                               size_t k, bool montgomery = true) const {
+        if (proofs.size() != k) throw std::invalid_argument("Groth16Verifier::aggregate_points: proofs are not k records");
+        weighted(inputs, z, k, "Groth16Verifier::aggregate_points");
+        std::vector<pa_g1_affine> out(k + 3);
+        check(pa_groth16_verify_aggregate_points(vk_, proofs.data(), inputs.data(), n_inputs(), flags(montgomery),
+                                                 z.data(), k, out.data()),
+              "Groth16Verifier::aggregate_points");
+        return out;
+    }
+
 private:
     static unsigned flags(bool montgomery) { return montgomery ? PA_MSM_SCALARS_MONTGOMERY : PA_MSM_SCALARS_REPR; }
     void sized(const std::vector<pa_fr>& inputs, size_t k, const char* what) const {
         if (inputs.size() != k * n_inputs())
             throw std::invalid_argument(std::string(what) + ": inputs are not k vectors of n_inputs() rows");
     }
+    void weighted(const std::vector<pa_fr>& inputs, const std::vector<uint64_t>& z, size_t k, const char* what) const {
+        sized(inputs, k, what);
+        if (z.size() != 2 * k) throw std::invalid_argument(std::string(what) + ": z is not k weights of two words");
+    }
     pa_groth16_vk* vk_ = nullptr;
 };
 inline Groth16Verifier verifier(const pa_groth16_vkey& key) { return Groth16Verifier(key); }
+
+// sum_i s_i P_i for 128-bit scalars (two little-endian words each) over per-call bases (pa_g1_multiexp_u128): the
+// same point as the multiexp over the zero-extended scalars, in about half the windows
+inline pa_g1 g1_multiexp_u128(const std::vector<pa_g1_affine>& bases, const std::vector<uint64_t>& scalars) {
+    if (scalars.size() != 2 * bases.size())
+        throw std::invalid_argument("g1_multiexp_u128: scalars are not one 128-bit row per base");
+    pa_g1 out;
+    check(pa_g1_multiexp_u128(bases.data(), scalars.data(), bases.size(), &out), "g1_multiexp_u128");
+    return out;
+}
 
 using G1Uncompressed = Encoded<G1Affine, 1, false>;
 using G1Compressed = Encoded<G1Affine, 1, true>;

@@ -241,6 +241,16 @@ _SIGS.update({
     "pa_groth16_verify": [_P, _P, _P, _N, ctypes.c_uint, _N, _P, _P],
     "pa_groth16_verify_encoded_device": [_P, _P, _P, _N, ctypes.c_uint, _N, _P, _P, _P, _P, _N, _P],
     "pa_groth16_verify_encoded": [_P, _P, _P, _N, ctypes.c_uint, _N, _P, _P, _P],
+    "pa_g1_multiexp_u128_workspace_bytes": [_N],                   # these two return size_t (below)
+    "pa_groth16_verify_aggregate_workspace_bytes": [_P, _N],
+    "pa_g1_multiexp_u128_device": [_P, _P, _N, _P, _P, _N, _P],
+    "pa_g1_multiexp_u128": [_P, _P, _N, _P],
+    "pa_groth16_verify_aggregate_device": [_P, _P, _P, _N, ctypes.c_uint, _P, _N, _P, _P, _P, _N, _P],
+    "pa_groth16_verify_aggregate": [_P, _P, _P, _N, ctypes.c_uint, _P, _N, _P, _P],
+    "pa_groth16_verify_aggregate_encoded_device": [_P, _P, _P, _N, ctypes.c_uint, _P, _N, _P, _P, _P, _P, _N, _P],
+    "pa_groth16_verify_aggregate_encoded": [_P, _P, _P, _N, ctypes.c_uint, _P, _N, _P, _P, _P],
+    "pa_groth16_verify_aggregate_points_device": [_P, _P, _P, _N, ctypes.c_uint, _P, _N, _P, _P, _N, _P],
+    "pa_groth16_verify_aggregate_points": [_P, _P, _P, _N, ctypes.c_uint, _P, _N, _P],
 })
 for _name, _args in _SIGS.items():
     _fn = getattr(_lib, _name)
@@ -268,7 +278,8 @@ for _name in ("pa_fr_ntt_domain_bytes", "pa_fr_ntt_polys_per_workgroup", "pa_fr_
     getattr(_lib, _name).restype = ctypes.c_size_t
 for _name in ("pa_r1cs_rows", "pa_r1cs_cols", "pa_r1cs_bytes", "pa_r1cs_eval_workspace_bytes", "pa_r1cs_chunk_len",
               "pa_groth16_prove_workspace_bytes", "pa_groth16_vk_n_public", "pa_groth16_vk_bytes",
-              "pa_groth16_vk_input_sum_workspace_bytes", "pa_groth16_verify_workspace_bytes"):
+              "pa_groth16_vk_input_sum_workspace_bytes", "pa_groth16_verify_workspace_bytes",
+              "pa_g1_multiexp_u128_workspace_bytes", "pa_groth16_verify_aggregate_workspace_bytes"):
     getattr(_lib, _name).restype = ctypes.c_size_t
 _lib.pa_r1cs_chunk_len.argtypes = []
 for _name in ("pa_r1cs_free", "pa_groth16_pk_free", "pa_groth16_vk_free"):
@@ -697,7 +708,7 @@ class Groth16VKey(ctypes.Structure):
 class Groth16Vk(_Handle):
     """A pa_groth16_vk handle: a verifying key prepared on one device -- e(alpha, beta),
     -gamma and -delta (affine and prepared), ic[0] and a fixed-base comb table for each of
-    ic[1..l].  `n_public` counts the constant one, `n_inputs` = n_public - 1 is the l of a
+    ic[1..l]; for the aggregate check the comb tables of ic[0] and alpha and -beta.  `n_public` counts the constant one, `n_inputs` = n_public - 1 is the l of a
     verify call, `bytes` the device memory held."""
 
     WHAT = "Groth16 verifying key"
@@ -736,9 +747,13 @@ class Groth16Vk(_Handle):
         if k < 0:
             raise ValueError("k must not be negative, got %d" % k)
         n = int(getattr(_lib, name)(self.handle(), k))
-        if n == 0 and k and (name == "pa_groth16_verify_workspace_bytes" or self.n_inputs):
+        if n == 0 and k and (name != "pa_groth16_vk_input_sum_workspace_bytes" or self.n_inputs):
             raise ValueError("a batch of %d proofs is over PA_GROTH16_VERIFY_MAX_BATCH: split it" % k)
         return n
+
+    def verify_aggregate_workspace_bytes(self, k):
+        """pa_groth16_verify_aggregate_workspace_bytes, for the three aggregate entries (never 0)"""
+        return self._bytes("pa_groth16_verify_aggregate_workspace_bytes", k)
 
     def verify_workspace_bytes(self, k):
         """pa_groth16_verify_workspace_bytes; a batch over the limit is a ValueError: split it"""

@@ -19,6 +19,7 @@
 #include "env.h"
 #include "launch.h"
 #include "launch_groth16.h"
+#include "launch_groth16_aggregate.h"
 #include "launch_groth16_verify.h"
 #include "launch_msm.h"
 
@@ -1577,6 +1578,36 @@ int pa_g2_multiexp_device(const pa_g2_affine* bases, const pa_fr_repr* scalars, 
     return PA_OK;
 }
 
+// 128-bit scalars over per-call bases: the 130-bit window plan, no endomorphism (kernels_msm.hip)
+size_t pa_g1_multiexp_u128_workspace_bytes(size_t n) { return pa::msm_u128_workspace_bytes(n); }
+int pa_g1_multiexp_u128_device(const pa_g1_affine* bases, const uint64_t* scalars, size_t n, pa_g1* out,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    if (!out || (n && (!bases || !scalars || !workspace))) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n >= 0x80000000ull) return fail(PA_ERR_INVALID_ARGUMENT, "multiexp supports n < 2^31");
+    if ((uintptr_t)scalars & 15) return fail(PA_ERR_INVALID_ARGUMENT, "scalars are not 16-byte aligned");
+    if (n && workspace_bytes < pa::msm_u128_workspace_bytes(n))
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_g1_multiexp_u128_workspace_bytes");
+    PA_TRY(pa::launch_msm_u128_g1((const uint64_t*)bases, scalars, n, (uint64_t*)out, workspace, workspace_bytes,
+                                  (hipStream_t)stream),
+           "kernel launch");
+    return PA_OK;
+}
+int pa_g1_multiexp_u128(const pa_g1_affine* bases, const uint64_t* scalars, size_t n, pa_g1* out) {
+    if (!out || (n && (!bases || !scalars))) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n >= 0x80000000ull) return fail(PA_ERR_INVALID_ARGUMENT, "multiexp supports n < 2^31");
+    DevBuf db, ds, dout, dws;
+    int rc;
+    if ((rc = upload(db, bases, sizeof(pa_g1_affine) * n)) || (rc = upload(ds, scalars, 16 * n))) return rc;
+    PA_TRY(dout.alloc(sizeof(pa_g1)), "device scratch");
+    const size_t ws = pa::msm_u128_workspace_bytes(n);
+    PA_TRY(dws.alloc(ws), "device scratch");
+    if ((rc = pa_g1_multiexp_u128_device(db.as<pa_g1_affine>(), ds.as<uint64_t>(), n, dout.as<pa_g1>(), dws.p, ws,
+                                         call_stream())))
+        return rc;
+    PA_TRY(call_sync(), "kernel execution");
+    return download(out, dout, sizeof(pa_g1));
+}
+
 // ---- MSM over prepared bases, G1 and G2 (kernels_msm.hip) ----
 // The object owns the 2n lazy rows on one device and remembers whether every
 // base passed the group's membership test: the host picks the GLV pipeline
@@ -2329,10 +2360,12 @@ struct pa_groth16_vk {
     int dev = 0;
     size_t n_public = 0, bytes = 0;
     // one allocation: e(alpha, beta), -gamma and -delta (affine, next to each other), ic[0], the two
-    // pa_g2_prepared records (-gamma, then -delta), the l comb tables
+    // pa_g2_prepared records (-gamma, then -delta), the l comb tables of ic[1..l]; for the aggregate check the
+    // comb tables of ic[0] and alpha behind them (tables l and l + 1) and -gamma, -delta, -beta (affine, next to
+    // each other: the tail of its Q array)
     uint64_t* mem = nullptr;
     const uint64_t *e_ab = nullptr, *neg_gamma = nullptr, *neg_delta = nullptr, *ic0 = nullptr, *prep_gamma = nullptr,
-                   *prep_delta = nullptr, *tables = nullptr;
+                   *prep_delta = nullptr, *tables = nullptr, *q_tail = nullptr;
     size_t inputs() const { return n_public - 1; }
 };
 
@@ -2468,10 +2501,18 @@ int pa_groth16_vk_create(const pa_groth16_vkey* key, pa_groth16_vk** out) {
     memcpy(head + 72 + 2 * kG2Words, &key->ic[0], sizeof(pa_g1_affine));
     // only the flag byte of a record's last word is defined
     for (size_t w : {72 + kG2Words - 1, 72 + 2 * kG2Words - 1, kHead - 1}) head[w] &= 0xff;
-    // ic[1..l] as the Jacobian records the table builder reads
-    std::vector<pa_g1> bases(l);
-    for (size_t i = 0; i < l; i++) {
-        const pa_g1_affine& a = key->ic[i + 1];
+    // -gamma, -delta, -beta: the last three Q records of the aggregate check
+    constexpr size_t kTail = 3 * kG2Words;
+    uint64_t tail[kTail];
+    pa_g2_affine neg_beta = key->beta_g2;
+    g2_affine_negate(neg_beta);
+    memcpy(tail, neg, sizeof neg);
+    memcpy(tail + 2 * kG2Words, &neg_beta, sizeof neg_beta);
+    for (size_t w : {kG2Words - 1, 2 * kG2Words - 1, 3 * kG2Words - 1}) tail[w] &= 0xff;
+    // ic[1..l], then ic[0] and alpha, as the Jacobian records the table builder reads
+    std::vector<pa_g1> bases(l + 2);
+    for (size_t i = 0; i < l + 2; i++) {
+        const pa_g1_affine& a = i < l ? key->ic[i + 1] : (i == l ? key->ic[0] : key->alpha_g1);
         memset(&bases[i], 0, sizeof(pa_g1));
         if (a.infinity) {
             memcpy(bases[i].y.l, kFqOne, sizeof kFqOne);
@@ -2484,13 +2525,14 @@ int pa_groth16_vk_create(const pa_groth16_vkey* key, pa_groth16_vk** out) {
     const size_t prep_at = align256(kHead * 8), tables_at = align256(prep_at + 2 * sizeof(pa_g2_prepared));
     pa_groth16_vk* vk = new pa_groth16_vk;
     vk->n_public = key->n_public;
-    vk->bytes = tables_at + l * table_words * 8;
+    const size_t tail_at = align256(tables_at + (l + 2) * table_words * 8);
+    vk->bytes = tail_at + kTail * 8;
     int rc = PA_OK;
     DevBuf dbases, dws;
     hipError_t e = hipGetDevice(&vk->dev);
     if (e == hipSuccess) e = hipMalloc((void**)&vk->mem, vk->bytes);
     if (e != hipSuccess) rc = fail(hip_code(e), "create Groth16 verifying key", e);
-    if (!rc) rc = upload(dbases, bases.data(), l * sizeof(pa_g1));
+    if (!rc) rc = upload(dbases, bases.data(), (l + 2) * sizeof(pa_g1));
     if (!rc && (e = dws.alloc(pa::g1_comb_workspace_words() * 8)) != hipSuccess)
         rc = fail(hip_code(e), "device scratch", e);
     if (!rc) {
@@ -2502,11 +2544,13 @@ int pa_groth16_vk_create(const pa_groth16_vkey* key, pa_groth16_vk** out) {
         vk->prep_gamma = (const uint64_t*)(m + prep_at);
         vk->prep_delta = (const uint64_t*)(m + prep_at + sizeof(pa_g2_prepared));
         vk->tables = (const uint64_t*)(m + tables_at);
+        vk->q_tail = (const uint64_t*)(m + tail_at);
         const hipStream_t s = call_stream();
         e = hipMemcpyAsync(vk->mem, head, sizeof head, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(m + tail_at, tail, sizeof tail, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = pa::launch_g2_prepare(vk->neg_gamma, (uint64_t*)(m + prep_at), 2, s);
         // one table per base, the builder's scratch reused in stream order
-        for (size_t i = 0; i < l && e == hipSuccess; i++)
+        for (size_t i = 0; i < l + 2 && e == hipSuccess; i++)
             e = pa::launch_g1_comb_table(dbases.as<uint64_t>() + 18 * i, (uint64_t*)(m + tables_at) + table_words * i,
                                          dws.as<uint64_t>(), s);
         if (e == hipSuccess) e = call_sync();   // `head` and the scratch go out of scope
@@ -2650,6 +2694,222 @@ int pa_groth16_verify_encoded(const pa_groth16_vk* vk, const uint8_t* enc, const
                               unsigned flags, size_t k, uint8_t* valid, uint8_t* status, pa_fq12* gt) {
     if (k && !enc) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
     return verify_host(vk, nullptr, enc, inputs, input_stride, flags, k, valid, status, gt);
+}
+
+// ---- Groth16 aggregate check: k proofs in one randomised pairing product (kernels_groth16_aggregate.hip) ----
+namespace {
+// The workspace: the P array (A'_0.. | accS | CS | alphaS, k + 3 affine records) first, at the next multiple of 256
+// bytes the Q array (B_0.. | -gamma | -delta | -beta); then the Jacobian rows that become P, the A and C arrays,
+// the Miller values (the product runs in place), the one gt and ok byte, the weight sums and their partials, the
+// comb partials, the MSM's workspace and the encoded entry's staging.
+constexpr size_t kG1JacWords = sizeof(pa_g1) / 8;
+struct AggLayout {
+    size_t p, q, jac, a, c, miller, gt, ok, s, wpart, comb, msm, msm_bytes, enc_a, enc_b, enc_c, status, bytes;
+};
+AggLayout agg_layout(const pa_groth16_vk* vk, size_t k) {
+    AggLayout v{};
+    const size_t l = vk->inputs();
+    size_t o = 0;
+    v.p = o;      o = align256(o + (k + 3) * sizeof(pa_g1_affine));
+    v.q = o;      o = align256(o + (k + 3) * sizeof(pa_g2_affine));
+    v.jac = o;    o = align256(o + (k + 3) * sizeof(pa_g1));
+    v.a = o;      o = align256(o + k * sizeof(pa_g1_affine));
+    v.c = o;      o = align256(o + k * sizeof(pa_g1_affine));
+    v.miller = o; o = align256(o + (k + 3) * sizeof(pa_fq12));
+    v.gt = o;     o = align256(o + sizeof(pa_fq12));
+    v.ok = o;     o = align256(o + 2);   // the final exponentiation's ok byte, then the statuses' any-nonzero byte
+    v.s = o;      o = align256(o + (l + 1) * sizeof(pa_fr));
+    v.wpart = o;  o = align256(o + (size_t)pa::kGroth16WeightMaxBlocks * (l + 1) * sizeof(pa_fr));
+    v.comb = o;   o = align256(o + (l + 2) * sizeof(pa_g1));
+    v.msm_bytes = pa::msm_u128_workspace_bytes(k);   // never decreases with k, like every other term here
+    v.msm = o;    o = align256(o + v.msm_bytes);
+    v.enc_a = o;  o = align256(o + k * 48);
+    v.enc_b = o;  o = align256(o + k * 96);
+    v.enc_c = o;  o = align256(o + k * 48);
+    v.status = o; o = align256(o + 3 * k);
+    v.bytes = o;
+    return v;
+}
+// what the three device entries refuse before anything runs; fills the layout
+int agg_check(const pa_groth16_vk* vk, const void* inputs, size_t input_stride, unsigned flags, const void* z,
+              size_t k, const void* workspace, size_t workspace_bytes, void* stream, int* mont, AggLayout* v) {
+    if (int rc = vk_call_check(vk, inputs, input_stride, flags, k, mont)) return rc;
+    if (!workspace || (k && !z)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    if ((uintptr_t)z & 15) return fail(PA_ERR_INVALID_ARGUMENT, "z is not 16-byte aligned");
+    *v = agg_layout(vk, k);
+    if (workspace_bytes < v->bytes)
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_groth16_verify_aggregate_workspace_bytes");
+    return vk_stream_check(vk, stream);
+}
+// Behind the A, B and C arrays: the weight sums, A' = z A, the comb sums, the MSM, into_affine of the k + 3
+// Jacobian rows into the P array, the Q array's tail.
+int agg_points(const pa_groth16_vk* vk, const AggLayout& v, uint8_t* ws, const uint64_t* inputs, size_t input_stride,
+               int mont, const uint64_t* z, size_t k, hipStream_t s) {
+    const size_t l = vk->inputs();
+    uint64_t *jac = (uint64_t*)(ws + v.jac), *sums = (uint64_t*)(ws + v.s);
+    PA_TRY(pa::launch_groth16_weight_sums(z, inputs, input_stride, mont, l, k, (uint64_t*)(ws + v.wpart), sums, s),
+           "kernel launch");
+    PA_TRY(pa::launch_groth16_scale((const uint64_t*)(ws + v.a), z, k, jac, s), "kernel launch");
+    PA_TRY(pa::launch_groth16_comb_sum(vk->tables, sums, l, (uint64_t*)(ws + v.comb), jac + kG1JacWords * k,
+                                       jac + kG1JacWords * (k + 2), s),
+           "kernel launch");
+    PA_TRY(pa::launch_msm_u128_g1((const uint64_t*)(ws + v.c), z, k, jac + kG1JacWords * (k + 1), ws + v.msm,
+                                  v.msm_bytes, s),
+           "kernel launch");
+    PA_TRY(pa::launch_group_op(1, pa::GROUP_INTO_AFFINE, jac, nullptr, (uint64_t*)(ws + v.p), k + 3, s),
+           "kernel launch");
+    PA_TRY(hipMemcpyAsync((uint64_t*)(ws + v.q) + kG2Words * k, vk->q_tail, 3 * sizeof(pa_g2_affine),
+                          hipMemcpyDeviceToDevice, s),
+           "device copy");
+    return PA_OK;
+}
+// k + 3 Miller loops in one launch, their product, one final exponentiation, the compare with one
+int agg_pairing(const AggLayout& v, uint8_t* ws, size_t k, uint8_t* valid, const uint8_t* status_abc,
+                uint8_t* status_out, pa_fq12* gt, hipStream_t s) {
+    uint64_t* ml = (uint64_t*)(ws + v.miller);
+    uint64_t* out = gt ? (uint64_t*)gt : (uint64_t*)(ws + v.gt);
+    PA_TRY(pairing_ml_launch((const uint64_t*)(ws + v.p), (const uint64_t*)(ws + v.q), ml, k + 3, s), "kernel launch");
+    PA_TRY(pa::launch_fq12_product(ml, k + 3, ml, s), "kernel launch");
+    PA_TRY(fe_launch(ml, out, ws + v.ok, 1, s), "kernel launch");
+    PA_TRY(pa::launch_groth16_aggregate_finish(out, ws + v.ok, status_abc, status_out, ws + v.ok + 1, valid, k, 0, s),
+           "kernel launch");
+    return PA_OK;
+}
+}  // namespace
+
+size_t pa_groth16_verify_aggregate_workspace_bytes(const pa_groth16_vk* vk, size_t k) {
+    return vk && k <= PA_GROTH16_VERIFY_MAX_BATCH ? agg_layout(vk, k).bytes : 0;
+}
+
+int pa_groth16_verify_aggregate_points_device(const pa_groth16_vk* vk, const pa_groth16_proof* proofs,
+                                              const pa_fr* inputs, size_t input_stride, unsigned flags,
+                                              const uint64_t* z, size_t k, pa_g1_affine* out, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+    int mont = 0;
+    AggLayout v;
+    if (int rc = agg_check(vk, inputs, input_stride, flags, z, k, workspace, workspace_bytes, stream, &mont, &v))
+        return rc;
+    if (!out || (k && !proofs)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    const hipStream_t s = (hipStream_t)stream;
+    PA_TRY(pa::launch_groth16_split3((const uint64_t*)proofs, k, (uint64_t*)(ws + v.a), (uint64_t*)(ws + v.q),
+                                     (uint64_t*)(ws + v.c), s),
+           "kernel launch");
+    if (int rc = agg_points(vk, v, ws, (const uint64_t*)inputs, input_stride, mont, z, k, s)) return rc;
+    PA_TRY(hipMemcpyAsync(out, ws + v.p, (k + 3) * sizeof(pa_g1_affine), hipMemcpyDeviceToDevice, s), "device copy");
+    return PA_OK;
+}
+
+int pa_groth16_verify_aggregate_device(const pa_groth16_vk* vk, const pa_groth16_proof* proofs, const pa_fr* inputs,
+                                       size_t input_stride, unsigned flags, const uint64_t* z, size_t k,
+                                       uint8_t* valid, pa_fq12* gt, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    int mont = 0;
+    AggLayout v;
+    if (int rc = agg_check(vk, inputs, input_stride, flags, z, k, workspace, workspace_bytes, stream, &mont, &v))
+        return rc;
+    if (!valid || (k && !proofs)) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    const hipStream_t s = (hipStream_t)stream;
+    if (k == 0) {   // the empty product
+        PA_TRY(pa::launch_groth16_aggregate_finish((uint64_t*)gt, nullptr, nullptr, nullptr, nullptr, valid, 0, 1, s),
+               "kernel launch");
+        return PA_OK;
+    }
+    PA_TRY(pa::launch_groth16_split3((const uint64_t*)proofs, k, (uint64_t*)(ws + v.a), (uint64_t*)(ws + v.q),
+                                     (uint64_t*)(ws + v.c), s),
+           "kernel launch");
+    if (int rc = agg_points(vk, v, ws, (const uint64_t*)inputs, input_stride, mont, z, k, s)) return rc;
+    return agg_pairing(v, ws, k, valid, nullptr, nullptr, gt, s);
+}
+
+int pa_groth16_verify_aggregate_encoded_device(const pa_groth16_vk* vk, const uint8_t* enc, const pa_fr* inputs,
+                                               size_t input_stride, unsigned flags, const uint64_t* z, size_t k,
+                                               uint8_t* valid, uint8_t* status, pa_fq12* gt, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    int mont = 0;
+    AggLayout v;
+    if (int rc = agg_check(vk, inputs, input_stride, flags, z, k, workspace, workspace_bytes, stream, &mont, &v))
+        return rc;
+    if (!valid || (k && (!enc || !status))) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    const hipStream_t s = (hipStream_t)stream;
+    if (k == 0) {
+        PA_TRY(pa::launch_groth16_aggregate_finish((uint64_t*)gt, nullptr, nullptr, nullptr, nullptr, valid, 0, 1, s),
+               "kernel launch");
+        return PA_OK;
+    }
+    uint8_t* st = ws + v.status;
+    PA_TRY(pa::launch_groth16_gather(enc, k, ws + v.enc_a, ws + v.enc_b, ws + v.enc_c, s), "kernel launch");
+    // the checked decoders write the A, B and C arrays themselves (the point at infinity for a record that fails)
+    PA_TRY(pa::launch_decode(1, 1, 1, ws + v.enc_a, k, (uint64_t*)(ws + v.a), st, s), "kernel launch");
+    PA_TRY(pa::launch_decode(2, 1, 1, ws + v.enc_b, k, (uint64_t*)(ws + v.q), st + k, s), "kernel launch");
+    PA_TRY(pa::launch_decode(1, 1, 1, ws + v.enc_c, k, (uint64_t*)(ws + v.c), st + 2 * k, s), "kernel launch");
+    if (int rc = agg_points(vk, v, ws, (const uint64_t*)inputs, input_stride, mont, z, k, s)) return rc;
+    return agg_pairing(v, ws, k, valid, st, status, gt, s);
+}
+
+namespace {
+// the host entries: one stream round trip.  what: 0 verify, 1 encoded, 2 points
+int agg_host(int what, const pa_groth16_vk* vk, const void* proofs, const pa_fr* inputs, size_t input_stride,
+             unsigned flags, const uint64_t* z, size_t k, uint8_t* valid, uint8_t* status, pa_fq12* gt,
+             pa_g1_affine* points) {
+    int mont = 0;
+    if (int rc = vk_call_check(vk, inputs, input_stride, flags, k, &mont)) return rc;
+    if ((what == 2 ? !points : !valid) || (k && (!proofs || !z || (what == 1 && !status))))
+        return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    DevBuf dproofs, din, dz, dflags, dgt, dpts, dws;
+    int rc;
+    if ((rc = upload(dproofs, proofs, k * (what == 1 ? PA_GROTH16_ENCODED_PROOF_BYTES : sizeof(pa_groth16_proof)))))
+        return rc;
+    if ((rc = upload(din, inputs, input_rows(vk, input_stride, k) * sizeof(pa_fr)))) return rc;
+    if ((rc = upload(dz, z, 16 * k))) return rc;
+    PA_TRY(dflags.alloc(1 + 3 * k), "device scratch");   // valid, then the 3 k statuses
+    if (gt) PA_TRY(dgt.alloc(sizeof(pa_fq12)), "device scratch");
+    if (what == 2) PA_TRY(dpts.alloc((k + 3) * sizeof(pa_g1_affine)), "device scratch");
+    const size_t ws = agg_layout(vk, k).bytes;
+    PA_TRY(dws.alloc(ws), "device scratch");
+    const hipStream_t s = call_stream();
+    uint8_t* dvalid = dflags.as<uint8_t>();
+    pa_fq12* dg = gt ? dgt.as<pa_fq12>() : nullptr;
+    if (what == 0)
+        rc = pa_groth16_verify_aggregate_device(vk, dproofs.as<pa_groth16_proof>(), din.as<pa_fr>(), input_stride,
+                                                flags, dz.as<uint64_t>(), k, dvalid, dg, dws.p, ws, s);
+    else if (what == 1)
+        rc = pa_groth16_verify_aggregate_encoded_device(vk, dproofs.as<uint8_t>(), din.as<pa_fr>(), input_stride,
+                                                        flags, dz.as<uint64_t>(), k, dvalid, dvalid + 1, dg, dws.p,
+                                                        ws, s);
+    else
+        rc = pa_groth16_verify_aggregate_points_device(vk, dproofs.as<pa_groth16_proof>(), din.as<pa_fr>(),
+                                                       input_stride, flags, dz.as<uint64_t>(), k,
+                                                       dpts.as<pa_g1_affine>(), dws.p, ws, s);
+    if (rc) return rc;
+    if (what == 2) {
+        PA_TRY(hipMemcpyAsync(points, dpts.p, (k + 3) * sizeof(pa_g1_affine), hipMemcpyDeviceToHost, s), "D2H copy");
+    } else {
+        PA_TRY(hipMemcpyAsync(valid, dvalid, 1, hipMemcpyDeviceToHost, s), "D2H copy");
+        if (what == 1 && k) PA_TRY(hipMemcpyAsync(status, dvalid + 1, 3 * k, hipMemcpyDeviceToHost, s), "D2H copy");
+        if (gt) PA_TRY(hipMemcpyAsync(gt, dgt.p, sizeof(pa_fq12), hipMemcpyDeviceToHost, s), "D2H copy");
+    }
+    PA_TRY(hipStreamSynchronize(s), "kernel execution");
+    return PA_OK;
+}
+}  // namespace
+
+int pa_groth16_verify_aggregate(const pa_groth16_vk* vk, const pa_groth16_proof* proofs, const pa_fr* inputs,
+                                size_t input_stride, unsigned flags, const uint64_t* z, size_t k, uint8_t* valid,
+                                pa_fq12* gt) {
+    return agg_host(0, vk, proofs, inputs, input_stride, flags, z, k, valid, nullptr, gt, nullptr);
+}
+int pa_groth16_verify_aggregate_encoded(const pa_groth16_vk* vk, const uint8_t* enc, const pa_fr* inputs,
+                                        size_t input_stride, unsigned flags, const uint64_t* z, size_t k,
+                                        uint8_t* valid, uint8_t* status, pa_fq12* gt) {
+    return agg_host(1, vk, enc, inputs, input_stride, flags, z, k, valid, status, gt, nullptr);
+}
+int pa_groth16_verify_aggregate_points(const pa_groth16_vk* vk, const pa_groth16_proof* proofs, const pa_fr* inputs,
+                                       size_t input_stride, unsigned flags, const uint64_t* z, size_t k,
+                                       pa_g1_affine* out) {
+    return agg_host(2, vk, proofs, inputs, input_stride, flags, z, k, nullptr, nullptr, nullptr, out);
 }
 
 // ---- CurveProjective / CurveAffine surface, G1 and G2 (kernels_group.hip) ----

@@ -39,4 +39,22 @@ PA_DEV void comb_add_entry(FlJac& acc, bool& untouched, bool& changed, const uin
     }
 }
 
+// acc = s T's base over the table's 33 comb rows (s: an FrRepr's four words, any value below 2^256): signed 8-bit
+// digits, at most 33 mixed additions, no doubling.  `untouched` stays true when nothing was added (the result
+// is the reference's zero()).
+PA_DEV void comb_mul_repr(FlJac& acc, bool& untouched, const uint64_t* table_fl, const uint64_t (&s)[4]) {
+    acc = {fl_zero(), fl_one(), fl_zero()};
+    untouched = true;
+    bool changed = false;
+    int carry = 0;
+#pragma unroll 1
+    for (int win = 0; win < kCombWindows; win++) {
+        int d = carry;
+        if (win < 32) d += (int)((s[win >> 3] >> (8 * (win & 7))) & 0xff);
+        carry = d > 128 ? 1 : 0;
+        if (d > 128) d -= 256;
+        if (d != 0) comb_add_entry(acc, untouched, changed, table_fl, win, d, false);
+    }
+}
+
 }  // namespace pa

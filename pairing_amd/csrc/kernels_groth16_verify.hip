@@ -61,17 +61,9 @@ __global__ void __launch_bounds__(64) k_g16v_partials(const uint64_t* __restrict
         for (int w = 0; w < 4; w++) s[w] = (uint64_t)r.w[2 * w] | ((uint64_t)r.w[2 * w + 1] << 32);
     }
     const uint64_t* table = tables + kCombTableWords * i;
-    FlJac acc = {fl_zero(), fl_one(), fl_zero()};
-    bool untouched = true, changed = false;
-    int carry = 0;
-#pragma unroll 1
-    for (int win = 0; win < kCombWindows; win++) {
-        int d = carry;
-        if (win < 32) d += (int)((s[win >> 3] >> (8 * (win & 7))) & 0xff);
-        carry = d > 128 ? 1 : 0;
-        if (d > 128) d -= 256;
-        if (d != 0) comb_add_entry(acc, untouched, changed, table, win, d, false);
-    }
+    FlJac acc;
+    bool untouched;
+    comb_mul_repr(acc, untouched, table, s);
     uint64_t* o = partials + (size_t)kG1Jac * t;
     if (untouched) {
         Jac<Fq> z;

@@ -57,6 +57,11 @@
 // j's window w is window j W + w, its items gather the same rows, the window
 // parts are ranges of vectors and k_msm_horner_batch_q runs every vector's
 // Horner chain side by side.  The digit kernels take Montgomery Fr rows too.
+//
+// 128-bit scalars over per-call G1 bases (launch_msm_u128_g1): a third plan,
+// k_msm_digits_u128 over 16-byte rows in the GLV plan's ceil(130 / c) windows
+// with n real terms -- no split, no endomorphism, no membership assumption; the
+// bases are converted per call as in the plain entry.
 
 #include <vector>
 
@@ -282,7 +287,9 @@ static uint32_t msm_parts_batch(size_t k) {
 }
 
 // `n` terms per window; the windows cover 257 bits for the plain entries (a
-// 256-bit FrRepr and the last carry), 130 for the GLV halves (glv; < 2^129).
+// 256-bit FrRepr and the last carry), 130 for the GLV halves (glv; < 2^129)
+// and for 128-bit scalars over n real terms (the u128 entry passes glv too:
+// the same window rule, no endomorphism, bases converted per call).
 // own_basefl: the workspace holds the per-call converted bases.
 // k > 1: a batch of k scalar vectors over the same bases, k W windows.
 static hipError_t msm_plan(MsmPlan& p, int group, size_t n, bool glv = false, bool own_basefl = true, size_t k = 1) {
@@ -441,6 +448,50 @@ __global__ void __launch_bounds__(256) k_msm_digits_glv(const uint64_t* __restri
                 keys[at] = (win0 + w) * B + (mag - 1);
                 vals[at] = row | (d < 0 ? 0x80000000u : 0u);
             }
+        }
+    }
+}
+
+// 128-bit scalars in 16-byte rows (two u64, little-endian) over n real terms:
+// the items of k_msm_digits in the 130-bit plan's windows.  c W >= 130 and the
+// scalar is below 2^128, so the top window's raw digit is below 2^(c-2): with
+// the carry at most 2^(c-2) <= B, never a carry out (2^128 - 1 recodes to -1
+// and a 1 at bit 128, inside the top window).
+__global__ void __launch_bounds__(256) k_msm_digits_u128(const uint64_t* __restrict__ scalars, size_t n, uint32_t c,
+                                                         uint32_t W, uint32_t B, uint32_t sentinel,
+                                                         uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 row = reinterpret_cast<const uint4*>(scalars)[i];
+    const uint64_t v0 = (uint64_t)row.x | ((uint64_t)row.y << 32), v1 = (uint64_t)row.z | ((uint64_t)row.w << 32);
+    const uint32_t mask = (1u << c) - 1;
+    uint32_t carry = 0;
+    for (uint32_t w = 0; w < W; w++) {
+        const uint32_t bit = w * c;
+        uint32_t raw = 0;
+        if (bit < 128) {
+            const uint32_t word = bit >> 6, sh = bit & 63;
+            uint64_t v = (word == 0 ? v0 : v1) >> sh;
+            if (sh + c > 64 && word == 0) v |= v1 << (64 - sh);
+            raw = (uint32_t)v & mask;
+        }
+        raw += carry;
+        int d;
+        if (raw > B) {
+            d = (int)raw - (int)(1u << c);
+            carry = 1;
+        } else {
+            d = (int)raw;
+            carry = 0;
+        }
+        const size_t at = (size_t)w * n + i;
+        if (d == 0) {
+            keys[at] = sentinel;
+            vals[at] = (uint32_t)i;
+        } else {
+            const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+            keys[at] = w * B + (mag - 1);
+            vals[at] = (uint32_t)i | (d < 0 ? 0x80000000u : 0u);
         }
     }
 }
@@ -1382,6 +1433,7 @@ struct MsmJob {
     bool glv;
     size_t vectors = 1;   // scalar vectors of `terms` rows end to end, one output each
     bool mont = false;    // the scalar rows are Montgomery Fr (< r), not FrRepr
+    bool u128 = false;    // the scalar rows are 16 bytes (< 2^128): the 130-bit plan over `terms` real terms
 };
 
 // The group's kernels of steps 4-6 on the lazy core, and the lanes that
@@ -1448,7 +1500,10 @@ static MsmWs msm_ws(const MsmPlan& p, const MsmJob& job, void* ws) {
 // items is set to sentinel keys first.  n: items per window.
 static hipError_t msm_sort_items(const MsmJob& job, const MsmPlan& p, size_t n, MsmWs& w, hipStream_t s) {
     const uint32_t WT = (uint32_t)p.WT, sentinel = WT * p.B;
-    if (job.glv)
+    if (job.u128)
+        hipLaunchKernelGGL(k_msm_digits_u128, dim3(msm_blocks(n, 256)), dim3(256), 0, s, job.scalars, n, p.c, p.W, p.B,
+                           sentinel, w.keys_in, w.vals_in);
+    else if (job.glv)
         hipLaunchKernelGGL(k_msm_digits_glv, dim3(msm_blocks(job.terms * job.vectors, 256)), dim3(256), 0, s,
                            job.scalars, job.terms, job.vectors, job.mont, (uint32_t)job.row_off, p.c, p.W, p.B,
                            sentinel, w.keys_in, w.vals_in);
@@ -1707,7 +1762,8 @@ static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_
     }
     const size_t n = job.glv ? 2 * job.terms : job.terms;   // items per window
     MsmPlan p;
-    hipError_t e = msm_plan(p, G, n, job.glv, job.rows == nullptr, job.vectors);
+    const bool short_plan = job.glv || job.u128;   // 130-bit windows
+    hipError_t e = msm_plan(p, G, n, short_plan, job.rows == nullptr, job.vectors);
     if (e != hipSuccess) return e;
     if (ws_bytes < p.total || !ws) return hipErrorInvalidValue;
     if (!p.fits || p.items > 0xffffffffull) return hipErrorInvalidValue;  // 32-bit item positions and keys
@@ -1715,7 +1771,7 @@ static hipError_t msm_run(const MsmJob& job, uint64_t* out, void* ws, size_t ws_
     MsmWs w = msm_ws(p, job, ws);
     if ((e = msm_sort_items(job, p, n, w, s)) != hipSuccess) return e;
     if ((e = msm_bounds_and_bases<G>(job, p, n, w, s)) != hipSuccess) return e;
-    const MsmStages<G> st(p, w, n, job.glv);
+    const MsmStages<G> st(p, w, n, short_plan);
     if (job.vectors > 1) return msm_schedule_batch<G>(st, job.vectors, out, s);
     return msm_schedule_windows<G>(st, out, s);
 }
@@ -1725,6 +1781,41 @@ hipError_t launch_msm(int group, const uint64_t* bases, const uint64_t* scalars,
     if (n >= 0x80000000ull) return hipErrorInvalidValue;
     const MsmJob job{bases, nullptr, scalars, n, 0, false};
     return group == 1 ? msm_run<1>(job, out, ws, ws_bytes, stream) : msm_run<2>(job, out, ws, ws_bytes, stream);
+}
+
+// The largest plan of any n' <= n, so that the size never decreases with n: a
+// workspace sized for the largest batch serves every smaller one.  The plan
+// of one n is not monotone in two places.  The window width changes at
+// powers of two (fewer windows: fewer items), and inside one width the chunk
+// T = msm_chunk(items) rises by one each time W n' passes a multiple of
+// kMsmFillLanes * parts, which shortens the continuation array by 1 / T.
+// Between those points every array grows with n', so the maximum is at n, at
+// the last n' of a width, or at the last n' before a step of T.
+size_t msm_u128_workspace_bytes(size_t n) {
+    if (n == 0) return 0;
+    size_t best = 0;
+    auto probe = [&](size_t m, MsmPlan& p) {
+        if (msm_plan(p, 1, m, true) == hipSuccess && p.total > best) best = p.total;
+    };
+    for (size_t lo = 1; lo <= n; lo <<= 1) {
+        const size_t hi = n < 2 * lo - 1 ? n : 2 * lo - 1;   // the width's terms are [lo, hi]
+        MsmPlan p{};
+        probe(hi, p);
+        if (!p.W) return 0;
+        const size_t step = kMsmFillLanes * msm_parts(p.W);   // T = ceil(W n' / step), within 8 .. kMsmChunk
+        for (size_t j = 8 > p.W * lo / step ? 8 : p.W * lo / step; j < kMsmChunk && j * step / p.W < hi; j++) {
+            MsmPlan q;
+            if (j * step / p.W >= lo) probe(j * step / p.W, q);
+        }
+    }
+    return best;
+}
+hipError_t launch_msm_u128_g1(const uint64_t* bases, const uint64_t* scalars, size_t n, uint64_t* out, void* ws,
+                              size_t ws_bytes, hipStream_t stream) {
+    if (n >= 0x80000000ull) return hipErrorInvalidValue;
+    MsmJob job{bases, nullptr, scalars, n, 0, false};
+    job.u128 = true;
+    return msm_run<1>(job, out, ws, ws_bytes, stream);
 }
 
 hipError_t launch_msm_prepare_g1(const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows, uint32_t* bad,

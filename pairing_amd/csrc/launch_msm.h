@@ -17,6 +17,15 @@ hipError_t launch_scalar_mul(int group, int projective, const uint64_t* p, const
 size_t msm_workspace_bytes(int group, size_t n);
 hipError_t launch_msm(int group, const uint64_t* bases, const uint64_t* scalars, size_t n, uint64_t* out, void* ws,
                       size_t ws_bytes, hipStream_t stream);
+// G1 only: out[0] = sum_i scalars[i] * bases[i] for 128-bit scalars in 16-byte
+// rows (two u64, little-endian): ceil(130 / c) windows over the n real terms
+// with the GLV plan's window rule, the bases converted per call.  No
+// endomorphism and no membership assumption: the same point as launch_msm
+// over the zero-extended scalars for any on-curve bases.  The workspace size
+// is the largest plan of any n' <= n: it never decreases with n.
+size_t msm_u128_workspace_bytes(size_t n);
+hipError_t launch_msm_u128_g1(const uint64_t* bases, const uint64_t* scalars, size_t n, uint64_t* out, void* ws,
+                              size_t ws_bytes, hipStream_t stream);
 
 // ---- MSM over prepared bases ----
 // Prepared rows, G1: 2n records of 28 u32 (the lazy 14 x 28-bit x, y the bucket

@@ -495,6 +495,94 @@ def groth16_input_sum(vk, inputs, k, out, workspace=None, stride=None, montgomer
          ctypes.c_void_p(workspace.data_ptr()) if need else ctypes.c_void_p(0), need, _stream_ptr(stream))
 
 
+def groth16_verify_aggregate_workspace(vk, k, device):
+    """A device workspace sized for the three aggregate entries over k proofs
+    (pa_groth16_verify_aggregate_workspace_bytes)."""
+    if not isinstance(vk, Groth16Vk):
+        raise ValueError("vk must come from groth16_vk")
+    return torch.empty(vk.verify_aggregate_workspace_bytes(k), dtype=torch.uint8, device=device)
+
+
+def _aggregate_args(vk, k, inputs, stride, montgomery, z, workspace):
+    """the arguments the aggregate entries share, after the checks that need no device"""
+    if not isinstance(vk, Groth16Vk):
+        raise ValueError("vk must come from groth16_vk")
+    vk.handle()   # a closed object is rejected first
+    flag = msm_scalars(montgomery)
+    h, stride = vk.check_inputs(inputs.shape[0] if inputs is not None else 0, k, stride)
+    if z.dim() != 2 or tuple(z.shape) != (k, 2):
+        raise ValueError("z must have shape (%d, 2): one 128-bit weight per proof, got %s" % (k, tuple(z.shape)))
+    zp = _dptr(z, 2, "z")
+    need = vk.verify_aggregate_workspace_bytes(k)
+    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.dtype != torch.uint8 \
+            or workspace.numel() < need:
+        raise ValueError("workspace must be a contiguous uint8 CUDA tensor of >= %d bytes" % need)
+    x = _dptr(inputs, 4, "inputs") if vk.n_inputs and k else ctypes.c_void_p(0)
+    return h, x, stride, flag, zp, ctypes.c_void_p(workspace.data_ptr()), workspace.numel()
+
+
+def groth16_verify_aggregate(vk, proofs, inputs, z, valid, workspace, gt=None, stride=None, montgomery=True,
+                             stream=None):
+    """k = proofs.shape[0] Groth16 proofs checked in HBM by one randomised pairing product
+    (pa_groth16_verify_aggregate_device): proofs and inputs as for groth16_verify; z (k, 2) int64,
+    the 128-bit weights (little-endian words), which the caller draws from a cryptographic
+    generator; valid: one uint8; gt None or (1, 72) int64; workspace from
+    groth16_verify_aggregate_workspace.  Everything is enqueued on the stream.  One verdict for the
+    batch: when it is 0, groth16_verify finds the bad proofs.  Up to 2^10 proofs groth16_verify is
+    the faster call (5.6 ms against 7.5 at 2^10), at 2^14 and above this one is (10.2 against
+    12.3; 19.6 against 29.1 at 2^16; README.md)."""
+    k = proofs.shape[0]
+    h, x, stride, flag, zp, ws, ws_bytes = _aggregate_args(vk, k, inputs, stride, montgomery, z, workspace)
+    g = _dptr(gt, W_FQ12, "gt") if gt is not None else ctypes.c_void_p(0)
+    if gt is not None:
+        _rows(gt, 1, "gt")
+    call("pa_groth16_verify_aggregate_device", h, _dptr(proofs, W_PROOF, "proofs"), x, stride, flag, zp, k,
+         _flags(valid, 1, "valid"), g, ws, ws_bytes, _stream_ptr(stream))
+
+
+def groth16_verify_aggregate_encoded(vk, data, inputs, z, valid, status, workspace, gt=None, stride=None,
+                                     montgomery=True, stream=None):
+    """groth16_verify_aggregate for k = data.shape[0] proofs off the wire
+    (pa_groth16_verify_aggregate_encoded_device): data (k, 192) uint8; status (k, 3) uint8 gets the
+    decoders' codes, and any nonzero one makes the batch not valid."""
+    if not data.is_cuda or not data.is_contiguous() or data.dtype != torch.uint8 or data.dim() != 2 \
+            or data.shape[1] != 192:
+        raise ValueError("data must be a contiguous (k, 192) uint8 CUDA tensor")
+    k = data.shape[0]
+    h, x, stride, flag, zp, ws, ws_bytes = _aggregate_args(vk, k, inputs, stride, montgomery, z, workspace)
+    g = _dptr(gt, W_FQ12, "gt") if gt is not None else ctypes.c_void_p(0)
+    if gt is not None:
+        _rows(gt, 1, "gt")
+    call("pa_groth16_verify_aggregate_encoded_device", h, ctypes.c_void_p(data.data_ptr()), x, stride, flag, zp, k,
+         _flags(valid, 1, "valid"), _flags(status, 3 * k, "status"), g, ws, ws_bytes, _stream_ptr(stream))
+
+
+def groth16_aggregate_points(vk, proofs, inputs, z, out, workspace, stride=None, montgomery=True, stream=None):
+    """The G1 side of the aggregate check into the first k + 3 rows of `out` ((rows, 13) int64 affine
+    records: z_j A_j | the weighted input sum | sum_j z_j C_j | s_0 alpha;
+    pa_groth16_verify_aggregate_points_device)."""
+    k = proofs.shape[0]
+    h, x, stride, flag, zp, ws, ws_bytes = _aggregate_args(vk, k, inputs, stride, montgomery, z, workspace)
+    _rows(out, k + 3, "out")
+    call("pa_groth16_verify_aggregate_points_device", h, _dptr(proofs, W_PROOF, "proofs"), x, stride, flag, zp, k,
+         _dptr(out, W_G1A, "out"), ws, ws_bytes, _stream_ptr(stream))
+
+
+def multiexp_u128_workspace(n, device):
+    """A device workspace sized for multiexp_u128 over n terms (pa_g1_multiexp_u128_workspace_bytes)."""
+    nbytes = int(_lib.pa_g1_multiexp_u128_workspace_bytes(int(n)))
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
+def multiexp_u128(bases, scalars, out, workspace, stream=None):
+    """out (1, 18) = sum_i scalars[i] * bases[i] over G1 affine records (n, 13) and 128-bit scalars
+    (n, 2) int64, little-endian words (pa_g1_multiexp_u128_device)."""
+    if scalars.shape[0] != bases.shape[0]:
+        raise ValueError("bases and scalars differ in length: %d vs %d" % (bases.shape[0], scalars.shape[0]))
+    call("pa_g1_multiexp_u128_device", _dptr(bases, W_G1A, "bases"), _dptr(scalars, 2, "scalars"), bases.shape[0],
+         _dptr(out, W_G1, "out"), ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
+
+
 def multiexp_workspace(group, n, device):
     """A device workspace sized for pa_g{group}_multiexp_device over n terms."""
     nbytes = int(_lib.pa_multiexp_workspace_bytes(int(group), int(n)))
