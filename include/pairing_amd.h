@@ -638,9 +638,15 @@ int pa_r1cs_eval(const pa_r1cs *r, const pa_fr *host_witness, size_t k, unsigned
  * PA_ERR_INVALID_ARGUMENT for n_public > n_vars, h_len > 2^log_n or log_n >
  * PA_NTT_MAX_LOG_N.  pa_groth16_pk_in_subgroup is 1 if all five query sets
  * passed their membership test (the multiexps then take the GLV path); the
- * proof is the same either way.  alpha, beta and delta are not tested; for
- * delta the key also holds 2^i delta, i < 255, in both groups (109 KiB), which
- * the assembly sums instead of doubling.
+ * proof is the same either way.  alpha, beta and delta are not tested: alpha,
+ * beta and the query points may be any curve points, infinity included, and
+ * the proof is bit-exact for them, but delta_g1 / delta_g2 outside G1/G2 are
+ * undefined for the prover (the assembly forms C from s A0 + r B0 + (r s) delta
+ * with A0 = A - r delta_g1, B0 = B1 - s delta_g1 and r s reduced mod the group
+ * order, which is the formula below only for a delta whose order divides it;
+ * no verifier could use another key).  For delta the key also holds
+ * 2^i delta, i < 255, in both groups (109 KiB), which the assembly sums instead
+ * of doubling.
  *
  * pa_groth16_prove*: for proof j with witness w (n_vars rows), z = n_public, h
  * the n rows of pa_fr_ntt_quotient over pa_r1cs_eval of w, and r, s its
