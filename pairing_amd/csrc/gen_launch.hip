@@ -261,7 +261,13 @@ hipError_t launch_miller_loop_gen(int lanes, const uint64_t* p_aff, const uint64
 // One kernel per final exponentiation, in place or not (round 3: its
 // inversions run in the kernel by binary GCD and exp_by_x squares compressed,
 // Karabina; tools/pgen/kernels.py).  Round 2's form split around a separate
-// inversion kernel was removed in round 4.
+// inversion kernel was removed in round 4.  The hard part is one sequential
+// chain of five exp_by_x by the full x, each taking the top of |x| as 7 * 15
+// (hard_part_seq, exp_by_x_karabina).  Only r and one call's input are parked
+// across a call, so the code objects need fewer workspace slots per wave: a
+// kernel strides its waves by its own slot count (kcfg.py emit_prologue),
+// and launch() above allocates blocks x wave_bytes(), the largest count of
+// pa_gen_meta.h, which the build rewrites with the code objects.
 hipError_t launch_final_exp_gen(int lanes, const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n,
                                 hipStream_t stream) {
     return launch(lanes == 2 ? 3 : 1, in, out, ok, n, stream);

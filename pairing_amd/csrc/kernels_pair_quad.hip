@@ -48,11 +48,11 @@ __device__ __forceinline__ void pq_final_exp_body(const uint64_t* in, uint64_t* 
     pq::store12(out + 72 * i, r, !good, lane & 31);
     if (ok && (lane & 31) == 0) ok[i] = good ? 1 : 0;
 }
-// one wave per SIMD (512 registers, 476 B of scratch) -- rounds of 2048 ...
+// one wave per SIMD (512 registers, 216 B of scratch) -- rounds of 2048 ...
 __global__ void __launch_bounds__(64) k_pq_final_exp(const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n) {
     pq_final_exp_body(in, out, ok, n);
 }
-// ... or two (256 registers, 2 KB of scratch): slower per wave (2048 pairs:
+// ... or two (256 registers, 1.3 KB of scratch): slower per wave (2048 pairs:
 // 2.33 vs 2.17 ms) but 4096 at once (3.80 ms instead of two rounds, 4.33)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_pq_final_exp2w(const uint64_t* in, uint64_t* out, uint8_t* ok, size_t n) {

@@ -19,8 +19,10 @@
 //
 //   miller_loop     mod.rs:40-102 (reference-form G2 steps: the Miller
 //                   values are the reference's, bit for bit once canonical)
-//   final_exp       mod.rs:104-160 (cyclotomic squarings inside exp_by_x:
-//                   the result is the reference's, the exponent is unique)
+//   final_exp       mod.rs:104-160 (cyclotomic squarings inside exp_by_x,
+//                   the top of |x| as 7 * 15, the hard part as one sequential
+//                   chain of five exp_by_x: the same power of the same
+//                   element, so the result is the reference's bit for bit)
 #pragma once
 #include "bgcd.h"
 #include "dec_quad.h"
@@ -375,35 +377,45 @@ PA_DEV E12 inv12(const E12& a, bool& ok, const Lc& l) {
 }
 
 // ---------------- final exponentiation, mod.rs:104-160 ----------------
-// exp_by_x (mod.rs:116-121): f^|x| by square-and-multiply with cyclotomic
-// squarings, then the conjugation (x < 0)
-PA_DEV E12 exp_by_x(const E12& f, uint64_t x, const Lc& l) {
-    E12 r = f;
-    const int top = 63 - __builtin_clzll(x);
+// exp_by_x (mod.rs:116-121): f^|x| with cyclotomic squarings, then the
+// conjugation (x < 0), for f in the cyclotomic subgroup (conjugation is
+// inversion there).  |x| = 2^16 + 2^48 + 2^57 * 105 and 105 = 7 * 15: the
+// first seven squarings form f^105 as t7 = f^8 conj(f) (after squaring 3),
+// then t7^16 conj(t7) (after squaring 7); bits 56..0 follow by
+// square-and-multiply.  64 squarings and 4 products, where the leading bits
+// taken one by one cost 63 and 5 (a product is five levels, a squaring three).
+PA_DEV E12 exp_by_x(const E12& f, const Lc& l) {
+    constexpr uint64_t kX = 0xd201000000010000ull;
+    static_assert(kX == (1ull << 16) + (1ull << 48) + (105ull << 57) && 105 == 7 * 15, "exponent chain");
+    E12 r = f, s = f;   // s: the factor whose conjugate closes the current 2^k - 1
 #pragma unroll 1
-    for (int bit = top - 1; bit >= 0; bit--) {
+    for (int i = 63; i >= 0; i--) {   // wave-uniform branches
         r = cyc_sqr(r, l);
-        if ((x >> bit) & 1) r = mul12(r, f, l);   // wave-uniform
+        const bool top = i == 61 || i == 57;
+        if (top || (i < 57 && ((kX >> i) & 1))) {
+            r = mul12(r, top ? conj12(s, l) : f, l);
+            if (top) s = r;
+        }
     }
     return conj12(r, l);
 }
+// The hard part as one sequential chain: with E = exp_by_x (E(f) = f^x) the
+// steps of mod.rs:125-156 compose to r^lambda,
+//   lambda = (x - 1)^2 (x + p) (x^2 + p^2 - 1) + 3
+// (an identity of integer polynomials; tools/pgen/kernels.py hard_part_seq,
+// tests/test_fe_chain.py), taken factor by factor: five E by the full x, 7
+// products and 2 Frobenius maps against the reference chain's 8 and 3.  The
+// value is the same power of the same element, so every output bit stays.
 PA_DEV E12 final_exp(const E12& f, bool& ok, const Lc& l) {
-    constexpr uint64_t kX = 0xd201000000010000ull;
     const E12 f2 = inv12(f, ok, l);
     E12 r = mul12(conj12(f, l), f2, l);
     r = mul12(frob12(r, 2, l), r, l);
-    const E12 y0 = cyc_sqr(r, l);
-    E12 y1 = exp_by_x(y0, kX, l);
-    E12 y2 = exp_by_x(y1, kX >> 1, l);
-    y1 = mul12(conj12(mul12(y1, conj12(r, l), l), l), y2, l);
-    y2 = exp_by_x(y1, kX, l);
-    E12 y3 = exp_by_x(y2, kX, l);
-    y1 = conj12(y1, l);
-    y3 = mul12(y3, y1, l);
-    y1 = mul12(frob12(conj12(y1, l), 3, l), frob12(y2, 2, l), l);
-    y2 = mul12(mul12(exp_by_x(y3, kX, l), y0, l), r, l);
-    y1 = mul12(y1, y2, l);
-    return mul12(y1, frob12(y3, 1, l), l);
+    E12 t = mul12(exp_by_x(r, l), conj12(r, l), l);          // r^(x - 1)
+    t = mul12(exp_by_x(t, l), conj12(t, l), l);              // r^((x - 1)^2)
+    t = mul12(exp_by_x(t, l), frob12(t, 1, l), l);           // ^(x + p)
+    const E12 u = mul12(frob12(t, 2, l), conj12(t, l), l);   // ^(p^2 - 1)
+    t = mul12(exp_by_x(exp_by_x(t, l), l), u, l);            // ^(x^2 + p^2 - 1)
+    return mul12(t, mul12(cyc_sqr(r, l), r, l), l);          // r^3
 }
 
 // ---------------- Miller loop, mod.rs:40-102 ----------------

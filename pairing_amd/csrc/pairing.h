@@ -10,8 +10,11 @@
 // Bit-exactness: line coefficients depend on the Jacobian history of R, so
 // the two steps below compute the reference's exact field-value sequence.
 // The Miller-loop output and the final exponentiation output are field
-// values, so their internal arithmetic (e.g. cyclotomic squaring inside
-// exp_by_x) may differ from the reference while the bits stay identical.
+// values, so their internal arithmetic may differ from the reference while
+// the bits stay identical: cyclotomic squarings inside exp_by_x, and in the
+// throughput kernels (tools/pgen/kernels.py, pair_quad.h) the exponent chain
+// itself -- the top of |x| as 7 * 15 and the hard part as the sequential
+// chain r^((x - 1)^2 (x + p) (x^2 + p^2 - 1) + 3), the same power of r.
 #pragma once
 #include "curve.h"
 

@@ -97,7 +97,10 @@ PROGRAMS = {
     "ml": _mk(kernels.miller_loop_prog, kcfg.MillerLoopCfg, "pa_gen_miller_loop"),
     # default final exponentiation: lazy Fq4 squarings only (tower.TowerLazySq, -1.5 % time);
     # PGEN_FE_LAZY=0 / 1 builds the plain / fully lazy tower instead (A/B experiments)
-    "fe": _mk(lambda: kernels.final_exp_prog(lazy={"sq": "sq", "0": False, "1": True}[os.environ.get("PGEN_FE_LAZY", "sq")]),
+    # both final exponentiation kernels on kernels.built_chain(): the hard part as one sequential
+    # chain, the top of x as 7 * 15 (PGEN_HP_SEQ=0 / PGEN_X715=0: the former chain, A/B)
+    "fe": _mk(lambda: kernels.final_exp_prog(lazy={"sq": "sq", "0": False, "1": True}[os.environ.get("PGEN_FE_LAZY", "sq")],
+                                             **kernels.built_chain()),
               kcfg.FinalExpCfg, "pa_gen_final_exp"),
     # round 2's final exponentiation split around a separate base-field
     # inversion (no longer loaded by gen_launch.hip; built only on request)
@@ -124,7 +127,8 @@ PROGRAMS = {
     "tdec": _mk(lambda: __import__("unit_progs").dec_prog(), kcfg.FinalExpCfg, "pa_gen_tdec"),
     "tunit": _mk(lambda: __import__("unit_progs").unit_prog(), kcfg.FinalExpCfg, "pa_gen_tunit"),
     "tdec2": _mk(lambda: __import__("unit_progs").dec_prog(lanes=2), kcfg.FinalExpCfg2, "pa_gen_tdec2"),
-    "fe2": _mk(__import__("tower2").two_pass(lambda: kernels.final_exp_prog(lanes=2)), kcfg.FinalExpCfg2,
+    "fe2": _mk(__import__("tower2").two_pass(lambda: kernels.final_exp_prog(lanes=2, **kernels.built_chain())),
+                kcfg.FinalExpCfg2,
                 "pa_gen_final_exp2"),
     # lazy reduction (tower.TowerLazy): wide products, one reduction per output Fq
     # (measured slower; built only on request for A/B runs)

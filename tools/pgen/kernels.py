@@ -360,18 +360,41 @@ def exp_by_x(p, T, V, f, x, tag):
     return T.conj12(V.get12(res))
 
 
-def exp_by_x_karabina(p, T, V, xv, L, first_skip, tag="k"):
-    """exp_by_x (mod.rs:116-121) in place on the Fq12 variable `xv`, as
-    f^|x| = prod f^(2^i) over the set bits i of |x| = 0xd201000000010000
-    (16, 48, 57, 60, 62, 63), then conjugation (x < 0).  The powers up to
-    bit 57 come from ONE run of compressed (Karabina) squarings, saved at bits
-    16 and 48; those three are decompressed with one shared inversion
-    (Tower.batch_inv2 -> the in-kernel binary GCD); the 6 squarings between the
-    top bits run uncompressed (Granger-Scott) from f^(2^57), since another
-    decompression would cost more than they do.  Inside the hard part's loop
-    over its five calls (final_exp_prog): when bit `first_skip` of the loop
-    counter L is set the first run is one squaring shorter, which is the
-    exp_by_x(x >> 1) call (bits 15, 47, 56, 59, 61, 62)."""
+def built_chain():
+    """The exponent chain of the final exponentiation kernels the build makes
+    (build_gen.PROGRAMS "fe" / "fe2"), as final_exp_prog's keywords:
+      x715  the top of |x| as 7 * 15 (exp_by_x_karabina); PGEN_X715=0: the
+            former six squarings with a product after squarings 3, 5 and 6
+      seq   the hard part as one sequential chain (hard_part_seq);
+            PGEN_HP_SEQ=0: the reference's chain (hard_part_loop)
+    Both default to 1; both at 0 build the former program operation for
+    operation (A/B).  final_exp_prog called without them gives that former
+    program too: the reference's chain, which the programs and counts pinned
+    before the change (tests/test_pgen_lazy2.py) describe."""
+    return {"x715": os.environ.get("PGEN_X715", "1") == "1", "seq": os.environ.get("PGEN_HP_SEQ", "1") == "1"}
+
+
+def exp_by_x_karabina(p, T, V, xv, L=None, first_skip=None, tag="k", x715=False):
+    """exp_by_x (mod.rs:116-121) in place on the Fq12 variable `xv`: f^|x|,
+    then conjugation (x < 0), with
+        |x| = 0xd201000000010000 = 2^16 + 2^48 + 2^57 * 105,  105 = 7 * 15.
+    The powers g16, g48 and t = g57 = f^(2^57) come from ONE run of compressed
+    (Karabina) squarings, saved at bits 16 and 48; those three are decompressed
+    with one shared inversion (Tower.batch_inv2 -> the in-kernel binary GCD).
+    Above bit 57 the squarings run uncompressed (Granger-Scott), since another
+    decompression would cost more than they do.  Every value is in the
+    cyclotomic subgroup, where conjugation is inversion and costs nothing:
+        t7   = t^8 conj(t)        3 squarings, 1 product
+        t105 = t7^16 conj(t7)     4 squarings, 1 product
+        res  = (g16 g48) t105     2 products
+    -- 7 squarings and 4 Fq12 products, where the set bits 57, 60, 62, 63 taken
+    one by one cost 6 squarings and 5 products (x715 false: that form).
+    t, then t7, is parked in the two snapshots' homes, dead once g16 g48 is
+    formed, so the form needs no storage of its own.
+    first_skip (the reference's chain, hard_part_loop): when bit `first_skip`
+    of the loop counter L is set the first run is one squaring shorter, which
+    is the exp_by_x(x >> 1) call (bits 15, 47, 56, 59, 61, 62); None: every
+    call is by the full x."""
     bits = [i for i in range(X_ABS.bit_length()) if (X_ABS >> i) & 1]
     res, top = "kr%s_" % tag, "kt%s_" % tag
     one = p.lanes == 1   # lane pairs: a distributed Fq2 is one variable (<n>0)
@@ -398,11 +421,11 @@ def exp_by_x_karabina(p, T, V, xv, L, first_skip, tag="k"):
     saved, prev = [], 0
     for k, b in enumerate(bits[:3]):
         n = b - prev
-        if k == 0:
+        if k == 0 and first_skip is not None:
             n -= 1
         with p.loop(n):
             ksqr_state()
-        if k == 0:
+        if k == 0 and first_skip is not None:
             with p.if_bit(((1 << 8) - 1) & ~(1 << first_skip), L):
                 ksqr_state()
         prev = b
@@ -435,21 +458,51 @@ def exp_by_x_karabina(p, T, V, xv, L, first_skip, tag="k"):
         # 15% fewer workspace moves, FE 9.29 -> 9.11 ms (profiles/r04_kdec_order.txt)
         V.set12(top, fin(2))
         V.set12(res, T.mul12(fin(0), fin(1)))
-        V.set12(res, T.mul12(V.get12(res), V.get12(top)))
-    # the top bits: squarings 1..6 above bit 57, multiply after squarings 3, 5, 6
-    # (loop counter 5..0 -> bits 3, 1, 0 of the mask)
     assert [b - bits[2] for b in bits[3:]] == [3, 5, 6]
-    with p.loop(6) as L2:
-        V.set12(top, T.cyc_sqr(V.get12(top)))
-        with p.if_bit(0b1011, L2):
+    if not x715 or order == "0":
+        # the top bits one by one: squarings 1..6 above bit 57, multiply after
+        # squarings 3, 5, 6 (loop counter 5..0 -> bits 3, 1, 0 of the mask)
+        if order != "0":
             V.set12(res, T.mul12(V.get12(res), V.get12(top)))
+        with p.loop(6) as L2:
+            V.set12(top, T.cyc_sqr(V.get12(top)))
+            with p.if_bit(0b1011, L2):
+                V.set12(res, T.mul12(V.get12(res), V.get12(top)))
+    else:
+        # 1 + 8 + 32 + 64 = 105 = 7 * 15: top^8 conj(top) after squaring 3, its
+        # 16th power times its conjugate after squaring 7 (loop counter 6..0: the
+        # product at 4 and 0, the factor parked at 4).  The parked factor lives in
+        # the snapshots' homes (saved[0], saved[1]: read for the last time by
+        # fin(0) fin(1) above)
+        sv = (saved[0] + saved[1])[:12 if one else 6]
+
+        def get_sv():
+            g = [p.get(n) for n in sv]
+            xs = [(g[2 * i], g[2 * i + 1]) for i in range(6)] if one else g
+            return ((xs[0], xs[1], xs[2]), (xs[3], xs[4], xs[5]))
+
+        def park_top():
+            xs = [x for c6 in V.get12(top) for x in c6]
+            for n, v in zip(sv, [c for x2 in xs for c in x2] if one else xs):
+                p.set(n, v)
+
+        assert 1 + (1 << 3) + (1 << 5) + (1 << 6) == 7 * 15 == ((1 << 3) - 1) * ((1 << 4) - 1)
+        park_top()
+        with p.loop(7) as L2:
+            V.set12(top, T.cyc_sqr(V.get12(top)))
+            with p.if_bit(0b0010001, L2):
+                V.set12(top, T.mul12(V.get12(top), T.conj12(get_sv())))
+            with p.if_bit(0b0010000, L2):
+                park_top()
+        V.set12(res, T.mul12(V.get12(res), V.get12(top)))
     V.set12(xv, T.conj12(V.get12(res)))
 
 
-def hard_part_loop(p, T, V, r):
+def hard_part_loop(p, T, V, r, x715=False):
     """mod.rs:125-156 with the five exp_by_x calls as ONE loop body (counter
     4..0 = calls a..e; the code between calls runs in branches on the counter),
     so the final exponentiation's code holds one copy of exp_by_x.  Returns y1.
+    The reference's chain (final_exp_prog's seq false); the built kernels take hard_part_seq.
         a: y1 = E(y0)                b: y2 = E'(y1)  (x >> 1)
            y1 = conj(y1 conj(r)) y2  c: y2 = E(y1)   d: y3 = E(y2)
            y1 = frob3(conj(conj(y1) ...)) ... (see below)    e: y2 = E(y3)"""
@@ -461,7 +514,7 @@ def hard_part_loop(p, T, V, r):
     V.set12("y0", y0)
     V.set12("x", y0)
     with p.loop(5) as L:
-        exp_by_x_karabina(p, T, V, "x", L, first_skip=3)
+        exp_by_x_karabina(p, T, V, "x", L, first_skip=3, x715=x715)
         with p.if_bit(1 << 4, L):          # after a: y1 = E(y0)
             V.set12("y1", V.get12("x"))
         with p.if_bit(1 << 3, L):          # after b: y2 = E'(y1); y1 = conj(y1 conj(r)) y2
@@ -486,7 +539,7 @@ def hard_part_loop(p, T, V, r):
     return T.mul12(y1, T.frob12(V.get12("y2"), 1))
 
 
-def hard_part_loop_folded(p, T, V, r):
+def hard_part_loop_folded(p, T, V, r, x715=False):
     """mod.rs:125-156 as hard_part_loop, with every factor of the result folded
     into one accumulator `u` as soon as it exists, so at most two Fq12 values
     are parked across an exp_by_x (hard_part_loop parks up to four).  With
@@ -503,7 +556,7 @@ def hard_part_loop_folded(p, T, V, r):
     V.set12("u", r)
     V.set12("x", T.cyc_sqr(r))
     with p.loop(5) as L:
-        exp_by_x_karabina(p, T, V, "x", L, first_skip=3)
+        exp_by_x_karabina(p, T, V, "x", L, first_skip=3, x715=x715)
         with p.if_bit(1 << 4, L):          # after a: y1 = E(r^2)
             V.set12("v", V.get12("x"))
         with p.if_bit(1 << 3, L):          # after b: Y = conj(y1 conj(r)) y2; u = Y^(q^3) conj(Y)^q r^3
@@ -520,12 +573,51 @@ def hard_part_loop_folded(p, T, V, r):
     return T.mul12(V.get12("u"), V.get12("x"))
 
 
+def hard_part_seq(p, T, V, r, x715=False):
+    """The hard part as ONE sequential chain.  With E(f) = f^x (x < 0:
+    E(f) = conj(f^|x|)) the steps of mod.rs:125-156 compose to r^lambda,
+        lambda = (x - 1)^2 [p^3 + x p^2 + (x^2 - 1) p + x (x^2 - 1)] + 3
+               = (x - 1)^2 (x + p) (x^2 + p^2 - 1) + 3
+    (an identity of integer polynomials, tests/test_fe_chain.py), and the
+    factors are taken one after the other:
+        a: t0 = E(r) conj(r)                        r^(x - 1)
+        b: t1 = E(t0) conj(t0)                      r^((x - 1)^2)
+        c: t2 = E(t1) frob(t1, 1)                   t1^(x + p)
+        d, e: t3 = E(E(t2)) [frob(t2, 2) conj(t2)]  t2^(x^2 + p^2 - 1)
+        result = t3 (r^2 r)
+    -- five exp_by_x by the full x (no x >> 1 call), 7 Fq12 products and 2
+    Frobenius maps against hard_part_loop's 8 and 3, and only r and the
+    current call's input are parked across a call (hard_part_loop parks hr, y0,
+    y1, y2).  As there, the five calls are ONE loop body (counter 4..0 = calls
+    a..e) with the code between them in branches on the counter, so the
+    program holds one copy of exp_by_x."""
+    H = os.environ.get("PGEN_HP_HOME", "M")
+    for n in ("hr", "t", "x"):
+        V.declare12(n, H)
+    V.set12("hr", r)
+    V.set12("x", r)
+    with p.loop(5) as L:
+        with p.if_bit(0b11110, L):         # before a..d: keep the call's input
+            V.set12("t", V.get12("x"))
+        exp_by_x_karabina(p, T, V, "x", x715=x715)
+        with p.if_bit(0b11000, L):         # after a, b: E(t) conj(t)
+            V.set12("x", T.mul12(V.get12("x"), T.conj12(V.get12("t"))))
+        with p.if_bit(0b00100, L):         # after c: E(t1) frob(t1, 1)
+            V.set12("x", T.mul12(V.get12("x"), T.frob12(V.get12("t"), 1)))
+    # after e: x = E(E(t2)), t = t2
+    t2 = V.get12("t")
+    t3 = T.mul12(V.get12("x"), T.mul12(T.frob12(t2, 2), T.conj12(t2)))
+    hr = V.get12("hr")
+    return T.mul12(t3, T.mul12(T.cyc_sqr(hr), hr))
+
+
 def _karabina():
     return os.environ.get("PGEN_KARABINA", "1") == "1"
 
 
-def final_exp_prog(lanes=1, lazy=False, tower_cls=None, split=None):
+def final_exp_prog(lanes=1, lazy=False, tower_cls=None, split=None, x715=False, seq=False):
     """lazy: False (Tower), True (TowerLazy) or "sq" (TowerLazySq);
+    x715, seq: the exponent chain (built_chain; false: the reference's chain);
     tower_cls overrides the tower class (coop.py: inversion as one op).
     split (one lane): the final exponentiation in two kernels around a
     base-field inversion run elsewhere (binary GCD, bgcd.h) instead of the
@@ -569,8 +661,13 @@ def final_exp_prog(lanes=1, lazy=False, tower_cls=None, split=None):
     f2 = r
     r = T.mul12(T.frob12(r, 2), f2)
     if kara:
-        hp = hard_part_loop_folded if os.environ.get("PGEN_HP_FOLD", "0") == "1" else hard_part_loop
-        V.store12(hp(p, T, V, r))
+        # seq false: the reference's chain (hard_part_loop; with PGEN_HP_FOLD=1 its
+        # folded form)
+        if seq:
+            hp = hard_part_seq
+        else:
+            hp = hard_part_loop_folded if os.environ.get("PGEN_HP_FOLD", "0") == "1" else hard_part_loop
+        V.store12(hp(p, T, V, r, x715=x715))
         return p
     x = X_ABS
     y0 = T.cyc_sqr(r)
