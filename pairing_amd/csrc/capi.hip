@@ -1639,15 +1639,12 @@ struct DeviceScope {
     }
 };
 
-// the group's records, launchers and the entry names its messages quote
+// the group's records and the entry names its messages quote
 template <int G> struct MsmAbi;
 template <> struct MsmAbi<1> {
     using Bases = pa_g1_msm_bases;
     using Affine = pa_g1_affine;
     using Point = pa_g1;
-    static constexpr auto prepare = pa::launch_msm_prepare_g1;
-    static constexpr auto single = pa::launch_msm_prepared_g1;
-    static constexpr auto batch = pa::launch_msm_prepared_g1_batch;
     static constexpr const char* small_ws = "workspace smaller than pa_g1_multiexp_prepared_workspace_bytes";
     static constexpr const char* small_batch_ws =
         "workspace smaller than pa_g1_multiexp_prepared_batch_workspace_bytes";
@@ -1656,9 +1653,6 @@ template <> struct MsmAbi<2> {
     using Bases = pa_g2_msm_bases;
     using Affine = pa_g2_affine;
     using Point = pa_g2;
-    static constexpr auto prepare = pa::launch_msm_prepare_g2;
-    static constexpr auto single = pa::launch_msm_prepared_g2;
-    static constexpr auto batch = pa::launch_msm_prepared_g2_batch;
     static constexpr const char* small_ws = "workspace smaller than pa_g2_multiexp_prepared_workspace_bytes";
     static constexpr const char* small_batch_ws =
         "workspace smaller than pa_g2_multiexp_prepared_batch_workspace_bytes";
@@ -1693,7 +1687,7 @@ int msm_bases_prepare_device(const typename MsmAbi<G>::Affine* bases, size_t n, 
     if (e == hipSuccess) e = hipMalloc((void**)&scratch, bad_off + sizeof(uint32_t));
     uint32_t* dbad = reinterpret_cast<uint32_t*>(scratch + bad_off);
     if (e == hipSuccess) e = pa::launch_subgroup_check(G, (const uint64_t*)bases, n, scratch, s);
-    if (e == hipSuccess) e = MsmAbi<G>::prepare((const uint64_t*)bases, scratch, n, b->rows, dbad, s);
+    if (e == hipSuccess) e = pa::launch_msm_prepare(G, (const uint64_t*)bases, scratch, n, b->rows, dbad, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, s);
     const hipError_t sync = hipStreamSynchronize(s);   // also before the scratch goes, whatever failed above
     if (e == hipSuccess) e = sync;
@@ -1736,8 +1730,8 @@ int msm_prepared_device(const typename MsmAbi<G>::Bases* b, const pa_fr_repr* sc
     int dev = 0;
     PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
     if (dev != b->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the prepared bases");
-    PA_TRY(MsmAbi<G>::single(b->rows, b->n, b->in_subgroup != 0, (const uint64_t*)scalars, m, (uint64_t*)out,
-                             workspace, workspace_bytes, (hipStream_t)stream),
+    PA_TRY(pa::launch_msm_prepared(G, b->rows, b->n, b->in_subgroup != 0, (const uint64_t*)scalars, m, 1, false,
+                                   (uint64_t*)out, workspace, workspace_bytes, (hipStream_t)stream),
            "kernel launch");
     return PA_OK;
 }
@@ -1784,9 +1778,9 @@ int msm_prepared_batch_device(const typename MsmAbi<G>::Bases* b, const void* sc
     int dev = 0;
     PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
     if (dev != b->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the prepared bases");
-    PA_TRY(MsmAbi<G>::batch(b->rows, b->n, b->in_subgroup != 0, (const uint64_t*)scalars, m, k,
-                            (flags & PA_MSM_SCALARS_MONTGOMERY) != 0, (uint64_t*)out, workspace, workspace_bytes,
-                            (hipStream_t)stream),
+    PA_TRY(pa::launch_msm_prepared(G, b->rows, b->n, b->in_subgroup != 0, (const uint64_t*)scalars, m, k,
+                                   (flags & PA_MSM_SCALARS_MONTGOMERY) != 0, (uint64_t*)out, workspace,
+                                   workspace_bytes, (hipStream_t)stream),
            "kernel launch");
     return PA_OK;
 }

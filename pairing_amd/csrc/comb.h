@@ -10,7 +10,7 @@ namespace pa {
 
 constexpr int kCombWindows = 33;      // 8-bit digits of a 255-bit scalar + final carry
 constexpr int kCombEntries = 128;     // |d| in 1..128
-constexpr int kG1Jac = 18;            // u64 words per Jacobian G1
+constexpr int kG1Jac = Grp<1>::JW;    // u64 words per Jacobian G1
 constexpr uint32_t kFlInfinity = 0xffffffffu;  // table entry marker: no lazy limb has all 32 bits set
 constexpr int kFlPair = 14;           // u64 words per table entry: x, y as 14 x 28-bit limbs (lazy core)
 // rows of the GLV form: 17 windows of each half (kernels_curve.hip); a table always has room for them
@@ -43,7 +43,7 @@ PA_DEV void comb_add_entry(FlJac& acc, bool& untouched, bool& changed, const uin
 // digits, at most 33 mixed additions, no doubling.  `untouched` stays true when nothing was added (the result
 // is the reference's zero()).
 PA_DEV void comb_mul_repr(FlJac& acc, bool& untouched, const uint64_t* table_fl, const uint64_t (&s)[4]) {
-    acc = {fl_zero(), fl_one(), fl_zero()};
+    acc = FlJac::zero();
     untouched = true;
     bool changed = false;
     int carry = 0;

@@ -59,6 +59,19 @@ template <class F> struct FieldWords;
 template <> struct FieldWords<Fq> { static constexpr int n = 6; };
 template <> struct FieldWords<Fq2> { static constexpr int n = 12; };
 
+// the group's coordinate field and record widths
+template <int G> struct Grp;
+template <> struct Grp<1> {
+    using F = Fq;
+    static constexpr int AW = 13;  // u64 words per affine record (pa_g1_affine)
+    static constexpr int JW = 18;  // u64 words per Jacobian record (pa_g1)
+};
+template <> struct Grp<2> {
+    using F = Fq2;
+    static constexpr int AW = 25;
+    static constexpr int JW = 36;
+};
+
 template <class F>
 PA_DEV void jac_zero(Jac<F>& p) {  // ec.rs:224-230
     zero(p.x);

@@ -12,7 +12,9 @@ namespace pa {
 
 // ---- G1 Jacobian arithmetic on the lazy core (same field values as curve.h) ----
 struct FlJac {
+    using Core = Fq;   // the coordinate field on the 12-word core
     F<1> x, y, z;
+    static PA_DEV FlJac zero() { return {fl_zero(), fl_one(), fl_zero()}; }   // ec.rs:224-230
 };
 PA_DEV bool fl_eq(const F<1>& a, const F<1>& b) { return fl_is_zero(sub(a, b)); }
 
@@ -100,6 +102,44 @@ PA_DEV void fl_store_jac(uint64_t* p, const FlJac& a) {
     fl_store(p, a.x);
     fl_store(p + 6, a.y);
     fl_store(p + 12, a.z);
+}
+
+// the accumulator, or the reference's zero() when nothing was added to it
+// (`untouched`), written through the 12-word core as its kernels write it.
+// acc by value: a kernel's tail then compiles to the code of the open-coded branch.
+template <class J>
+PA_DEV void fl_store_jac_or_zero(uint64_t* p, J acc, bool untouched) {
+    if (untouched) {
+        Jac<typename J::Core> z;
+        jac_zero(z);
+        store_jac(p, z);
+    } else {
+        fl_store_jac(p, acc);
+    }
+}
+
+// An affine point as a lazy row: x, y as 14 u32 each, the infinity flag in
+// bit 31 of x's top limb (below 2^18 for F<1>), so one gather of 28 u32
+// fetches the point and its flag; the gather clears the flag in x
+PA_DEV void fl_pack_row(uint32_t* d, const F<1>& x, const F<1>& y, bool inf) {
+#pragma unroll
+    for (int k = 0; k < 14; k++) {
+        d[k] = x.w[k] | (k == 13 && inf ? 0x80000000u : 0u);
+        d[14 + k] = y.w[k];
+    }
+}
+PA_DEV void fl_gather_row(const uint32_t* row, F<1>& x, F<1>& y, bool& inf) {
+    const uint2* src = reinterpret_cast<const uint2*>(row);
+#pragma unroll
+    for (int q = 0; q < 7; q++) {
+        const uint2 a = src[q], b = src[7 + q];
+        x.w[2 * q] = a.x;
+        x.w[2 * q + 1] = a.y;
+        y.w[2 * q] = b.x;
+        y.w[2 * q + 1] = b.y;
+    }
+    inf = (x.w[13] >> 31) != 0;
+    x.w[13] &= 0x7fffffffu;
 }
 
 PA_DEV F<1> fl_from_lane(const F<1>& x, int src) {

@@ -235,16 +235,10 @@ __global__ void __launch_bounds__(64) k_g1_comb_mul(const uint64_t* __restrict__
     for (int w = 0; w < 4; w++) s[w] = scalars[4 * i + w];
     const bool flip = wnaf_wrap(s, window);   // the reference's digits spell -(2^256 - s)
     uint64_t* o = out + (size_t)kG1Jac * i;
-    FlJac acc;
+    FlJac acc = FlJac::zero();
     bool untouched = true, changed = false;
-    if (first) {
-        acc.x = fl_zero();
-        acc.y = fl_one();
-        acc.z = fl_zero();
-    } else {
-        acc.x = fl_load(o);
-        acc.y = fl_load(o + 6);
-        acc.z = fl_load(o + 12);
+    if (!first) {
+        acc = fl_load_jac(o);
         untouched = false;  // a zero (z == 0) is caught by fl_jac_add_mixed
     }
     int carry = 0;
@@ -274,15 +268,7 @@ __global__ void __launch_bounds__(64) k_g1_comb_mul(const uint64_t* __restrict__
         }
     }
     if (!first && !changed) return;
-    if (untouched) {
-        Jac<Fq> z;
-        jac_zero(z);
-        store_jac(o, z);
-    } else {
-        fl_store(o, acc.x);
-        fl_store(o + 6, acc.y);
-        fl_store(o + 12, acc.z);
-    }
+    fl_store_jac_or_zero(o, acc, untouched);
 }
 
 // GLV membership flag: *flag = kGateGlv iff phi(P) == -[x^2] P (or P is
@@ -358,16 +344,10 @@ __global__ void __launch_bounds__(64) k_g1_glv_mul(const uint64_t* __restrict__ 
     const int neg = wnaf_wrap(s, window) ? 1 : 0;   // -(2^256 - s): every digit negated
     glv_split(s, rem, q);
     uint64_t* o = out + (size_t)kG1Jac * i;
-    FlJac acc;
+    FlJac acc = FlJac::zero();
     bool untouched = true, changed = false;
-    if (first) {
-        acc.x = fl_zero();
-        acc.y = fl_one();
-        acc.z = fl_zero();
-    } else {
-        acc.x = fl_load(o);
-        acc.y = fl_load(o + 6);
-        acc.z = fl_load(o + 12);
+    if (!first) {
+        acc = fl_load_jac(o);
         untouched = false;
     }
     int cr = 0, cq = 0;
@@ -392,14 +372,12 @@ __global__ void __launch_bounds__(64) k_g1_glv_mul(const uint64_t* __restrict__ 
             comb_add_entry(acc, untouched, changed, table_fl, (step & 1) * kGlvWindows + win, d, (step & 1) ^ neg);
     }
     if (!first && !changed) return;
-    if (untouched) {
+    if (untouched) {   // fl_store_jac_or_zero, kept inline: through the helper two registers swap
         Jac<Fq> z;
         jac_zero(z);
         store_jac(o, z);
     } else {
-        fl_store(o, acc.x);
-        fl_store(o + 6, acc.y);
-        fl_store(o + 12, acc.z);
+        fl_store_jac(o, acc);
     }
 }
 
@@ -417,14 +395,14 @@ __global__ void __launch_bounds__(64) k_g1_fixed_base_ladder(const uint64_t* __r
     for (int w = 0; w < 4; w++) s[w] = scalars[4 * i + w];
     FlJac p = fl_load_jac(base);
     if (wnaf_wrap(s, window)) p.y = red(neg(p.y));   // (2^256 - s) (-P)
-    FlJac acc = {fl_zero(), fl_one(), fl_zero()};
+    FlJac acc = FlJac::zero();
 #pragma unroll 1
     for (int bit = 255; bit >= 0; bit--) {
         if (!fl_is_zero(acc.z)) fl_jac_double(acc);
         if ((s[bit >> 6] >> (bit & 63)) & 1) fl_jac_add(acc, p);
     }
     uint64_t* o = out + (size_t)kG1Jac * i;
-    if (fl_is_zero(acc.z)) {
+    if (fl_is_zero(acc.z)) {   // fl_store_jac_or_zero, kept inline: the helper changes the register allocation
         Jac<Fq> z;
         jac_zero(z);
         store_jac(o, z);

@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(64) k_g16a_scale(const uint64_t* __restrict__ 
         h[2] = d2 + (t1 < d1 ? 1 : 0) + (h[1] < t1 ? 1 : 0);
     }
     const F<1> px = fl_from_abi(p.x), py = fl_from_abi(p.y);
-    FlJac acc = {fl_zero(), fl_one(), fl_zero()};
+    FlJac acc = FlJac::zero();
     bool untouched = true;
 #pragma unroll 1
     for (int i = 128; i >= 0; i--) {
@@ -149,14 +149,7 @@ __global__ void __launch_bounds__(64) k_g16a_comb_partials(const uint64_t* __res
     FlJac acc;
     bool untouched;
     comb_mul_repr(acc, untouched, tables + kCombTableWords * t, w);
-    uint64_t* o = partials + (size_t)kG1Jac * t;
-    if (untouched) {
-        Jac<Fq> zero_pt;
-        jac_zero(zero_pt);
-        store_jac(o, zero_pt);
-    } else {
-        fl_store_jac(o, acc);
-    }
+    fl_store_jac_or_zero(partials + (size_t)kG1Jac * t, acc, untouched);
 }
 
 // out_acc = partial[0] + .. + partial[l] (one block of kSumLanes lanes: lane i adds partials i, i + 64, .. in
@@ -167,7 +160,7 @@ __global__ void __launch_bounds__(kSumLanes) k_g16a_comb_sum(const uint64_t* __r
     __shared__ FlJac sh[kSumLanes];
     const unsigned tid = threadIdx.x;
     if (tid < (unsigned)kG1Jac) out_alpha[tid] = partials[(size_t)kG1Jac * (l + 1) + tid];
-    FlJac acc = {fl_zero(), fl_one(), fl_zero()};
+    FlJac acc = FlJac::zero();
 #pragma unroll 1
     for (size_t t = tid; t <= l; t += kSumLanes) fl_jac_add(acc, fl_load_jac(partials + (size_t)kG1Jac * t));
     sh[tid] = acc;
@@ -180,15 +173,7 @@ __global__ void __launch_bounds__(kSumLanes) k_g16a_comb_sum(const uint64_t* __r
         }
         __syncthreads();
     }
-    if (tid == 0) {
-        if (fl_is_zero(acc.z)) {
-            Jac<Fq> zero_pt;
-            jac_zero(zero_pt);
-            store_jac(out_acc, zero_pt);
-        } else {
-            fl_store_jac(out_acc, acc);
-        }
-    }
+    if (tid == 0) fl_store_jac_or_zero(out_acc, acc, fl_is_zero(acc.z));
 }
 
 // one lane per word of a proof record; only the flag byte of a record's last word is defined

@@ -64,14 +64,7 @@ __global__ void __launch_bounds__(64) k_g16v_partials(const uint64_t* __restrict
     FlJac acc;
     bool untouched;
     comb_mul_repr(acc, untouched, table, s);
-    uint64_t* o = partials + (size_t)kG1Jac * t;
-    if (untouched) {
-        Jac<Fq> z;
-        jac_zero(z);
-        store_jac(o, z);
-    } else {
-        fl_store_jac(o, acc);
-    }
+    fl_store_jac_or_zero(partials + (size_t)kG1Jac * t, acc, untouched);
 }
 
 // out[j] = into_affine(ic0 + partial[j l] + ... + partial[j l + l - 1])

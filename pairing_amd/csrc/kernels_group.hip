@@ -27,18 +27,6 @@
 namespace pa {
 namespace {
 
-template <int G> struct Grp;
-template <> struct Grp<1> {
-    using F = Fq;
-    static constexpr int AW = 13;  // u64 words per affine record (pa_g1_affine)
-    static constexpr int JW = 18;  // u64 words per Jacobian record (pa_g1)
-};
-template <> struct Grp<2> {
-    using F = Fq2;
-    static constexpr int AW = 25;
-    static constexpr int JW = 36;
-};
-
 inline unsigned blocks_for(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
 // ---------------- per-op batches ----------------
@@ -229,24 +217,25 @@ __global__ void __launch_bounds__(64) k_comb_fill_fl2(const uint64_t* __restrict
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= kCombWindows * kCombEntries) return;
     const int i = e / kCombEntries, d = e % kCombEntries + 1;
-    const FlJac2 b = fl2_load_jac(bases + JW * i);
-    FlJac2 acc = fl2_jac_zero();
+    const FlJac2 b = fl_load_jac<2>(bases + JW * i);
+    FlJac2 acc = FlJac2::zero();
 #pragma unroll 1
     for (int bit = 7; bit >= 0; bit--) {
-        if (!f2_is_zero(acc.z)) fl2_jac_double(acc);
-        if ((d >> bit) & 1) fl2_jac_add(acc, b);
+        if (!fl_is_zero(acc.z)) fl_jac_double(acc);
+        if ((d >> bit) & 1) fl_jac_add(acc, b);
     }
-    if (f2_is_zero(acc.z)) {
+    if (fl_is_zero(acc.z)) {   // fl_store_jac_or_zero, kept inline: the helper changes the register allocation
         Jac<Fq2> z;
         jac_zero(z);
         store_jac(table_jac + (size_t)JW * e, z);
     } else {
-        fl2_store_jac(table_jac + (size_t)JW * e, acc);
+        fl_store_jac(table_jac + (size_t)JW * e, acc);
     }
 }
 
-// G2 table entries in the lazy core's limbs: x.c0, x.c1, y.c0, y.c1 as 14 u32
-// each, the infinity flag in bit 31 of x.c0's top limb (below 2^18 for F<1>)
+// G2 table entries in the lazy core's limbs, the MSM's G2 row layout: x.c0, x.c1,
+// y.c0, y.c1 as 14 u32 each, the infinity flag in bit 31 of x.c0's top limb
+// (below 2^18 for F<1>)
 constexpr int kFl2Words = 28;   // u64 per entry
 __global__ void __launch_bounds__(64) k_comb_pack_fl2(const uint64_t* __restrict__ table_jac,
                                                       uint64_t* __restrict__ table) {
@@ -275,7 +264,7 @@ __global__ void __launch_bounds__(64) k_comb_mul_fl2(const uint64_t* __restrict_
 #pragma unroll
     for (int w = 0; w < 4; w++) s[w] = scalars[4 * i + w];
     const bool flip = wnaf_wrap(s, window);   // the reference's digits spell -(2^256 - s)
-    FlJac2 acc = fl2_jac_zero();
+    FlJac2 acc = FlJac2::zero();
     bool untouched = true;
     int carry = 0;
 #pragma unroll 1
@@ -297,16 +286,9 @@ __global__ void __launch_bounds__(64) k_comb_mul_fl2(const uint64_t* __restrict_
         if ((c[0].w[13] >> 31) != 0) continue;   // an infinity entry: add_assign_mixed's no-op
         const F2<1> y = {c[2], c[3]};
         const F2<2> oy = ((d < 0) != flip) ? neg(y) : relax<2>(y);
-        fl2_jac_add_mixed(acc, untouched, F2<1>{c[0], c[1]}, oy);
+        fl_jac_add_mixed(acc, untouched, F2<1>{c[0], c[1]}, oy);
     }
-    uint64_t* o = out + (size_t)Grp<2>::JW * i;
-    if (untouched) {
-        Jac<Fq2> z;
-        jac_zero(z);
-        store_jac(o, z);
-    } else {
-        fl2_store_jac(o, acc);
-    }
+    fl_store_jac_or_zero(out + (size_t)Grp<2>::JW * i, acc, untouched);
 }
 
 }  // namespace

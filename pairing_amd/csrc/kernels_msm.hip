@@ -27,19 +27,20 @@
 //      for negative digits), run by run; k_msm_bucket_fix folds the pieces of
 //      buckets that span chunks and zeroes empty buckets (k_msm_long_fix: the
 //      buckets that span many).
-//   5. k_msm_segments_fl / _fl2: per window, sum_m m*B_m by running sums over
+//   5. k_msm_segments<G>: per window, sum_m m*B_m by running sums over
 //      segments of L buckets (T += B_m; S += T, top down), plus a*T for the
 //      segment offset.
 //   6. k_msm_group_sum_fl / _fl2 (repeated): segment results -> one sum per window.
 //   7. k_msm_horner_q: one group of lane quads, sum_w 2^(c*w) S_w.
-// Steps 4-6 run on the lazy 28-bit core for both groups (curve_fl.h, curve_fl2.h;
-// MsmKernels<G> names the group's kernels).
+// Steps 4-6 run on the lazy 28-bit core for both groups, written once over
+// curve_fl.h / curve_fl2.h's shared names; MsmKernels<G> names the kernels
+// that differ by group on purpose.
 // Steps 4-7 run per part of the windows (top windows first, msm_run): a part's
 // reduction (4's fix-up, 5, 6) and its Horner leg run on side streams while
 // the next part accumulates, so only the last part's tail is exposed.
 // Work: n*W mixed additions + ~2*W*2^(c-1) additions + ~256 doublings.
 //
-// MSM over prepared G1 bases (launch_msm_prepare_g1 / launch_msm_prepared_g1):
+// MSM over prepared G1 bases (launch_msm_prepare / launch_msm_prepared, group 1):
 // the bases are converted to the lazy rows once, row n + i = -phi(P_i) =
 // (beta x_i, -y_i) beside row i = P_i, and checked for G1 membership once.
 // When every base is in G1, k_msm_digits_glv splits each scalar s = q x^2 + rem
@@ -48,12 +49,12 @@
 // windows: the same msm_run with another digit kernel, term count and window
 // count (MsmJob).  Otherwise the 257-bit pipeline runs over rows [0, m).
 //
-// MSM over prepared G2 bases (launch_msm_prepare_g2 / launch_msm_prepared_g2):
+// MSM over prepared G2 bases (group 2):
 // the same over 56-word rows, with row n + i = (beta^2 x_i, -y_i) = x^2 Q_i
 // (kMsmBeta2): the split, the digit kernels and every stage are the G1 path's.
 //
 // A batch of k scalar vectors over the same prepared bases
-// (launch_msm_prepared_g1_batch / _g2_batch) is the same pipeline over k W windows: vector
+// (launch_msm_prepared with k > 1) is the same pipeline over k W windows: vector
 // j's window w is window j W + w, its items gather the same rows, the window
 // parts are ranges of vectors and k_msm_horner_batch_q runs every vector's
 // Horner chain side by side.  The digit kernels take Montgomery Fr rows too.
@@ -78,18 +79,6 @@
 #include <utility>
 
 namespace pa {
-
-template <int G> struct Grp;
-template <> struct Grp<1> {
-    using F = Fq;
-    static constexpr int AW = 13;  // u64 words per affine record (pa_g1_affine)
-    static constexpr int JW = 18;  // u64 words per Jacobian record (pa_g1)
-};
-template <> struct Grp<2> {
-    using F = Fq2;
-    static constexpr int AW = 25;
-    static constexpr int JW = 36;
-};
 
 // ---------------- per-lane scalar multiplication ----------------
 template <int G>
@@ -752,25 +741,36 @@ PA_DEV bool chunk_range(size_t i, const uint32_t* __restrict__ wpre, uint32_t w0
     return j0 < j1;
 }
 
-// G1 on the lazy 28-bit core: the affine bases converted once per MSM
-// (x, y -> 28 u32; the infinity flag in bit 31 of x's top limb, which is
-// below 2^18, so a bucket item gathers ONE 112-byte record) ...
+// The affine bases converted once per MSM to lazy rows (curve_fl.h's
+// fl_pack_row for G1: x, y -> 28 u32, the infinity flag inside, so a bucket
+// item gathers ONE 112-byte record; G2: x.c0, x.c1, y.c0, y.c1 -> 56 u32, the
+// flag in bit 31 of x.c0's top limb, below 2^18 for F<1>) ...
+// The G2 conversion and both prepare kernels keep their own store loops: through
+// a shared pack helper the compiler schedules their loads and stores differently.
+template <int G> constexpr int kMsmRowWords = 28 * G;
 __global__ void __launch_bounds__(256) k_msm_bases_fl(const uint64_t* __restrict__ bases, size_t n,
                                                       uint32_t* __restrict__ fl) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Aff<Fq> a;
     load_aff(a, bases + (size_t)Grp<1>::AW * i);
-    const F<1> x = fl_from_abi(a.x), y = fl_from_abi(a.y);
-    uint32_t* d = fl + 28 * i;
+    fl_pack_row(fl + kMsmRowWords<1> * i, fl_from_abi(a.x), fl_from_abi(a.y), a.inf);
+}
+__global__ void __launch_bounds__(256) k_msm_bases_fl2(const uint64_t* __restrict__ bases, size_t n,
+                                                       uint32_t* __restrict__ fl) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Aff<Fq2> a;
+    load_aff(a, bases + (size_t)Grp<2>::AW * i);
+    const F<1> v[4] = {fl_from_abi(a.x.c0), fl_from_abi(a.x.c1), fl_from_abi(a.y.c0), fl_from_abi(a.y.c1)};
+    uint32_t* d = fl + kMsmRowWords<2> * i;
 #pragma unroll
-    for (int k = 0; k < 14; k++) {
-        d[k] = x.w[k] | (k == 13 && a.inf ? 0x80000000u : 0u);
-        d[14 + k] = y.w[k];
-    }
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+        for (int k = 0; k < 14; k++) d[14 * c + k] = v[c].w[k] | (c == 0 && k == 13 && a.inf ? 0x80000000u : 0u);
 }
 
-// The prepared rows (launch_msm_prepare_g1): row i as k_msm_bases_fl writes
+// The prepared rows (launch_msm_prepare, group 1): row i as k_msm_bases_fl writes
 // it, row n + i = -phi(P_i) = (beta x_i, -y_i), an infinity base flagged in
 // both; the membership flags ok[i] (launch_subgroup_check) counted into *bad.
 // beta: kernels_curve.hip's kGlvBeta, the decode kernel's kBeta (Montgomery words)
@@ -789,8 +789,8 @@ __global__ void __launch_bounds__(256) k_msm_bases_prepare(const uint64_t* __res
     neg(ny, a.y);
     const F<1> x = fl_from_abi(a.x), y = fl_from_abi(a.y), px = fl_from_abi(bx), py = fl_from_abi(ny);
     const uint32_t inf = a.inf ? 0x80000000u : 0u;
-    uint32_t* d = rows + 28 * i;
-    uint32_t* e = rows + 28 * (n + i);
+    uint32_t* d = rows + kMsmRowWords<1> * i;
+    uint32_t* e = rows + kMsmRowWords<1> * (n + i);
 #pragma unroll
     for (int k = 0; k < 14; k++) {
         d[k] = x.w[k] | (k == 13 ? inf : 0u);
@@ -801,20 +801,55 @@ __global__ void __launch_bounds__(256) k_msm_bases_prepare(const uint64_t* __res
     if (!ok[i]) atomicAdd(bad, 1u);
 }
 
-PA_DEV void msm_flush_fl(uint32_t key, const FlJac& acc, bool untouched, size_t j0, size_t k,
-                         const uint32_t* __restrict__ start, uint64_t* __restrict__ buckets,
-                         uint64_t* __restrict__ cont) {
-    constexpr int JW = Grp<1>::JW;
-    uint64_t* o = start[key] >= j0 ? buckets + (size_t)JW * key : cont + (size_t)JW * k;
-    if (untouched) {
-        Jac<Fq> z;
-        jac_zero(z);
-        store_jac(o, z);
-    } else {
-        fl_store(o, acc.x);
-        fl_store(o + 6, acc.y);
-        fl_store(o + 12, acc.z);
-    }
+// The prepared G2 rows (launch_msm_prepare, group 2): row i as k_msm_bases_fl2
+// writes it, row n + i = x^2 Q_i = (beta^2 x_i, -y_i) with beta^2 scaling both Fq
+// components of x; an infinity base flagged in both; the membership flags
+// ok[i] (launch_subgroup_check) counted into *bad.
+// kMsmBeta2 is the square of kMsmBeta (Montgomery words), the other primitive
+// cube root of unity in Fq.  On G1 (x, y) -> (beta x, y) multiplies by -x^2,
+// one root of l^2 + l + 1 = 0 mod r; on the twist's subgroup G2 the same map
+// multiplies by the other root, (-x^2)^2 = x^2 - 1, so the map that multiplies
+// by -x^2 there, the one the split s = q x^2 + rem needs, is the one with
+// beta^2 (tests/test_msm_g2_prepared.py checks it against the oracle).
+__constant__ const uint64_t kMsmBeta2[6] = {0xcd03c9e48671f071ULL, 0x5dab22461fcda5d2ULL, 0x587042afd3851b95ULL,
+                                            0x8eb60ebe01bacb9eULL, 0x03f97d6e83d050d2ULL, 0x18f0206554638741ULL};
+__global__ void __launch_bounds__(256) k_msm_bases_prepare_g2(const uint64_t* __restrict__ bases,
+                                                              const uint8_t* __restrict__ ok, size_t n,
+                                                              uint32_t* __restrict__ rows,
+                                                              uint32_t* __restrict__ bad) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Aff<Fq2> a;
+    load_aff(a, bases + (size_t)Grp<2>::AW * i);
+    Fq beta2, bx0, bx1, ny0, ny1;
+    fq_load(beta2, kMsmBeta2);
+    mul(bx0, a.x.c0, beta2);
+    mul(bx1, a.x.c1, beta2);
+    neg(ny0, a.y.c0);
+    neg(ny1, a.y.c1);
+    const F<1> v[4] = {fl_from_abi(a.x.c0), fl_from_abi(a.x.c1), fl_from_abi(a.y.c0), fl_from_abi(a.y.c1)};
+    const F<1> p[4] = {fl_from_abi(bx0), fl_from_abi(bx1), fl_from_abi(ny0), fl_from_abi(ny1)};
+    const uint32_t inf = a.inf ? 0x80000000u : 0u;
+    uint32_t* d = rows + kMsmRowWords<2> * i;
+    uint32_t* e = rows + kMsmRowWords<2> * (n + i);
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+        for (int k = 0; k < 14; k++) {
+            const uint32_t flag = c == 0 && k == 13 ? inf : 0u;
+            d[14 * c + k] = v[c].w[k] | flag;
+            e[14 * c + k] = p[c].w[k] | flag;
+        }
+    if (!ok[i]) atomicAdd(bad, 1u);
+}
+
+// a finished run of one bucket: to the bucket when it starts inside the chunk, else to cont[k]
+template <int G>
+PA_DEV void msm_flush(uint32_t key, const FlPoint<G>& acc, bool untouched, size_t j0, size_t k,
+                      const uint32_t* __restrict__ start, uint64_t* __restrict__ buckets,
+                      uint64_t* __restrict__ cont) {
+    constexpr int JW = Grp<G>::JW;
+    fl_store_jac_or_zero(start[key] >= j0 ? buckets + (size_t)JW * key : cont + (size_t)JW * k, acc, untouched);
 }
 
 // ... and the bucket accumulation with the lazy mixed addition (curve_fl.h);
@@ -830,10 +865,7 @@ PA_DEV void chunk_acc_fl_body(const uint32_t* __restrict__ basefl, const uint32_
     if (!chunk_range((size_t)blockIdx.x * blockDim.x + threadIdx.x, wpre, w0, w1, T, k, j0, j1)) return;
     uint32_t cur = keys[j0];
     if (cur >= sentinel) return;
-    FlJac acc;
-    acc.x = fl_zero();
-    acc.y = fl_one();
-    acc.z = fl_zero();
+    FlJac acc = FlJac::zero();
     bool untouched = true;
     // software pipeline: the (key, value) pair two items ahead and the base
     // of the next item are in flight while the current mixed addition runs
@@ -848,20 +880,7 @@ PA_DEV void chunk_acc_fl_body(const uint32_t* __restrict__ basefl, const uint32_
     };
     auto gather = [&](uint32_t kk, uint32_t vv, F<1>& x, F<1>& y, bool& inf) {
         inf = true;
-        if (kk < sentinel) {
-            const uint32_t idx = vv & 0x7fffffffu;
-            const uint2* src = reinterpret_cast<const uint2*>(basefl + 28 * (size_t)idx);
-#pragma unroll
-            for (int q = 0; q < 7; q++) {
-                const uint2 a = src[q], b = src[7 + q];
-                x.w[2 * q] = a.x;
-                x.w[2 * q + 1] = a.y;
-                y.w[2 * q] = b.x;
-                y.w[2 * q + 1] = b.y;
-            }
-            inf = (x.w[13] >> 31) != 0;
-            x.w[13] &= 0x7fffffffu;
-        }
+        if (kk < sentinel) fl_gather_row(basefl + kMsmRowWords<1> * (size_t)(vv & 0x7fffffffu), x, y, inf);
     };
     uint32_t key0, v0, key1, v1;
     fetch(j0, key0, v0);
@@ -878,7 +897,7 @@ PA_DEV void chunk_acc_fl_body(const uint32_t* __restrict__ basefl, const uint32_
         bool ninf;
         gather(key1, v1, nx, ny, ninf);
         if (key0 != cur) {
-            msm_flush_fl(cur, acc, untouched, j0, k, start, buckets, cont);
+            msm_flush<1>(cur, acc, untouched, j0, k, start, buckets, cont);
             untouched = true;
             cur = key0;
         }
@@ -894,7 +913,7 @@ PA_DEV void chunk_acc_fl_body(const uint32_t* __restrict__ basefl, const uint32_
         ty = ny;
         inf = ninf;
     }
-    msm_flush_fl(cur, acc, untouched, j0, k, start, buckets, cont);
+    msm_flush<1>(cur, acc, untouched, j0, k, start, buckets, cont);
 }
 __global__ void __launch_bounds__(64) k_msm_chunk_acc_fl(const uint32_t* __restrict__ basefl,
                                                          const uint32_t* __restrict__ keys,
@@ -932,17 +951,10 @@ __global__ void __launch_bounds__(64) k_msm_bucket_fix(const uint32_t* __restric
         long_list[atomicAdd(long_count, 1u)] = (uint32_t)b;
         return;
     }
-    if constexpr (G == 1) {  // lazy core, same formulas and values
-        FlJac acc = fl_load_jac(buckets + (size_t)JW * b);
+    FlPoint<G> acc = fl_load_jac<G>(buckets + (size_t)JW * b);   // lazy core, same formulas and values
 #pragma unroll 1
-        for (size_t k = first + 1; k <= last; k++) fl_jac_add(acc, fl_load_jac(cont + (size_t)JW * k));
-        fl_store_jac(buckets + (size_t)JW * b, acc);
-    } else {
-        FlJac2 acc = fl2_load_jac(buckets + (size_t)JW * b);
-#pragma unroll 1
-        for (size_t k = first + 1; k <= last; k++) fl2_jac_add(acc, fl2_load_jac(cont + (size_t)JW * k));
-        fl2_store_jac(buckets + (size_t)JW * b, acc);
-    }
+    for (size_t k = first + 1; k <= last; k++) fl_jac_add(acc, fl_load_jac<G>(cont + (size_t)JW * k));
+    fl_store_jac(buckets + (size_t)JW * b, acc);
 }
 
 // out[w*stride + g] = sum_{k<group} in[w*stride + g*group + k]  (indices < count),
@@ -957,10 +969,7 @@ __global__ void __launch_bounds__(64) k_msm_group_sum_fl(const uint64_t* __restr
     if (t >= (size_t)w1 * gpw) return;
     const size_t w = t / gpw;
     const uint32_t g = (uint32_t)(t % gpw);
-    FlJac acc;
-    acc.x = fl_zero();
-    acc.y = fl_one();
-    acc.z = fl_zero();
+    FlJac acc = FlJac::zero();
 #pragma unroll 1
     for (uint32_t k = 0; k < group; k++) {
         const uint32_t idx = g * group + k;
@@ -1074,30 +1083,27 @@ __global__ void __launch_bounds__(64) k_msm_horner_batch_q(const uint64_t* __res
 // One lane per segment of L buckets of one window: sum_m m * B_m over the
 // segment, by running sums top down (T += B_m; S += T) plus a * T for the
 // segment's offset a.
-__global__ void __launch_bounds__(64) k_msm_segments_fl(const uint64_t* __restrict__ buckets, uint32_t B, uint32_t L,
-                                                        size_t t0, size_t t1, uint64_t* __restrict__ segs) {
-    // one lane per segment: the kernel is throughput bound (4 k waves); a quad
+template <int G>
+__global__ void __launch_bounds__(64) k_msm_segments(const uint64_t* __restrict__ buckets, uint32_t B, uint32_t L,
+                                                     size_t t0, size_t t1, uint64_t* __restrict__ segs) {
+    // one lane per segment: the kernel is throughput bound (4 k waves); a G1 quad
     // per segment (fl_jac_add_q) measured 0.57 -> 1.29 ms (profiles/r03_msm_quad_ab.txt)
-    constexpr int JW = Grp<1>::JW;
+    constexpr int JW = Grp<G>::JW;
     const size_t t = t0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= t1) return;
     const uint32_t spw = B / L;
     const size_t w = t / spw;
     const uint32_t j = (uint32_t)(t % spw);
     const uint64_t* bw = buckets + (size_t)JW * (w * B);
-    FlJac T, S;
-    T.x = fl_zero();
-    T.y = fl_one();
-    T.z = fl_zero();
-    S = T;
+    FlPoint<G> T = FlPoint<G>::zero(), S = T;
 #pragma unroll 1
     for (uint32_t m = (j + 1) * L; m > j * L; m--) {  // magnitudes (j*L, (j+1)*L], top down
-        fl_jac_add(T, fl_load_jac(bw + (size_t)JW * (m - 1)));
+        fl_jac_add(T, fl_load_jac<G>(bw + (size_t)JW * (m - 1)));
         fl_jac_add(S, T);
     }
     const uint32_t a = j * L;  // S = sum (m - a) B_m; add a * T
     if (a && !fl_is_zero(T.z)) {
-        FlJac aT = T;  // top set bit of a
+        FlPoint<G> aT = T;  // top set bit of a
         const int top = 31 - __clz(a);
 #pragma unroll 1
         for (int bit = top - 1; bit >= 0; bit--) {
@@ -1110,80 +1116,8 @@ __global__ void __launch_bounds__(64) k_msm_segments_fl(const uint64_t* __restri
 }
 
 
-// ---- G2 bucket phases on the lazy core's Fq2 (curve_fl2.h; round 4) ----
-// The affine bases converted once per MSM (x.c0, x.c1, y.c0, y.c1 -> 56 u32;
-// the infinity flag in bit 31 of x.c0's top limb, below 2^18 for F<1>) ...
-__global__ void __launch_bounds__(256) k_msm_bases_fl2(const uint64_t* __restrict__ bases, size_t n,
-                                                       uint32_t* __restrict__ fl) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Aff<Fq2> a;
-    load_aff(a, bases + (size_t)Grp<2>::AW * i);
-    const F<1> v[4] = {fl_from_abi(a.x.c0), fl_from_abi(a.x.c1), fl_from_abi(a.y.c0), fl_from_abi(a.y.c1)};
-    uint32_t* d = fl + 56 * i;
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-#pragma unroll
-        for (int k = 0; k < 14; k++) d[14 * c + k] = v[c].w[k] | (c == 0 && k == 13 && a.inf ? 0x80000000u : 0u);
-}
-
-// The prepared G2 rows (launch_msm_prepare_g2): row i as k_msm_bases_fl2 writes
-// it, row n + i = x^2 Q_i = (beta^2 x_i, -y_i) with beta^2 scaling both Fq
-// components of x; an infinity base flagged in both; the membership flags
-// ok[i] (launch_subgroup_check) counted into *bad.
-// kMsmBeta2 is the square of kMsmBeta (Montgomery words), the other primitive
-// cube root of unity in Fq.  On G1 (x, y) -> (beta x, y) multiplies by -x^2,
-// one root of l^2 + l + 1 = 0 mod r; on the twist's subgroup G2 the same map
-// multiplies by the other root, (-x^2)^2 = x^2 - 1, so the map that multiplies
-// by -x^2 there, the one the split s = q x^2 + rem needs, is the one with
-// beta^2 (tests/test_msm_g2_prepared.py checks it against the oracle).
-__constant__ const uint64_t kMsmBeta2[6] = {0xcd03c9e48671f071ULL, 0x5dab22461fcda5d2ULL, 0x587042afd3851b95ULL,
-                                            0x8eb60ebe01bacb9eULL, 0x03f97d6e83d050d2ULL, 0x18f0206554638741ULL};
-__global__ void __launch_bounds__(256) k_msm_bases_prepare_g2(const uint64_t* __restrict__ bases,
-                                                              const uint8_t* __restrict__ ok, size_t n,
-                                                              uint32_t* __restrict__ rows,
-                                                              uint32_t* __restrict__ bad) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Aff<Fq2> a;
-    load_aff(a, bases + (size_t)Grp<2>::AW * i);
-    Fq beta2, bx0, bx1, ny0, ny1;
-    fq_load(beta2, kMsmBeta2);
-    mul(bx0, a.x.c0, beta2);
-    mul(bx1, a.x.c1, beta2);
-    neg(ny0, a.y.c0);
-    neg(ny1, a.y.c1);
-    const F<1> v[4] = {fl_from_abi(a.x.c0), fl_from_abi(a.x.c1), fl_from_abi(a.y.c0), fl_from_abi(a.y.c1)};
-    const F<1> p[4] = {fl_from_abi(bx0), fl_from_abi(bx1), fl_from_abi(ny0), fl_from_abi(ny1)};
-    const uint32_t inf = a.inf ? 0x80000000u : 0u;
-    uint32_t* d = rows + 56 * i;
-    uint32_t* e = rows + 56 * (n + i);
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-#pragma unroll
-        for (int k = 0; k < 14; k++) {
-            const uint32_t flag = c == 0 && k == 13 ? inf : 0u;
-            d[14 * c + k] = v[c].w[k] | flag;
-            e[14 * c + k] = p[c].w[k] | flag;
-        }
-    if (!ok[i]) atomicAdd(bad, 1u);
-}
-
-PA_DEV void msm_flush_fl2(uint32_t key, const FlJac2& acc, bool untouched, size_t j0, size_t k,
-                          const uint32_t* __restrict__ start, uint64_t* __restrict__ buckets,
-                          uint64_t* __restrict__ cont) {
-    constexpr int JW = Grp<2>::JW;
-    uint64_t* o = start[key] >= j0 ? buckets + (size_t)JW * key : cont + (size_t)JW * k;
-    if (untouched) {
-        Jac<Fq2> z;
-        jac_zero(z);
-        store_jac(o, z);
-    } else {
-        fl2_store_jac(o, acc);
-    }
-}
-
-// ... the bucket accumulation with the lazy mixed addition; the (key, value) pair
+// ---- G2's own bucket phases on the lazy core's Fq2 (curve_fl2.h) ----
+// The bucket accumulation with the lazy mixed addition; the (key, value) pair
 // of the next item in flight while the current addition runs (a prefetched
 // 224-byte base would not fit beside the Fq2 temporaries)
 __global__ void __launch_bounds__(64) k_msm_chunk_acc_fl2(const uint32_t* __restrict__ basefl,
@@ -1197,7 +1131,7 @@ __global__ void __launch_bounds__(64) k_msm_chunk_acc_fl2(const uint32_t* __rest
     if (!chunk_range((size_t)blockIdx.x * blockDim.x + threadIdx.x, wpre, w0, w1, T, k, j0, j1)) return;
     uint32_t cur = keys[j0];
     if (cur >= sentinel) return;
-    FlJac2 acc = fl2_jac_zero();
+    FlJac2 acc = FlJac2::zero();
     bool untouched = true;
     uint32_t key = cur, v = vals[j0];
 #pragma unroll 1
@@ -1209,11 +1143,13 @@ __global__ void __launch_bounds__(64) k_msm_chunk_acc_fl2(const uint32_t* __rest
             nv = vals[j + 1];
         }
         if (key != cur) {
-            msm_flush_fl2(cur, acc, untouched, j0, k, start, buckets, cont);
+            msm_flush<2>(cur, acc, untouched, j0, k, start, buckets, cont);
             untouched = true;
             cur = key;
         }
-        const uint2* src = reinterpret_cast<const uint2*>(basefl + 56 * (size_t)(v & 0x7fffffffu));
+        // the row as k_msm_bases_fl2 wrote it, gathered inline (as k_comb_mul_fl2 does): through a
+        // shared helper this kernel's registers are allocated differently
+        const uint2* src = reinterpret_cast<const uint2*>(basefl + kMsmRowWords<2> * (size_t)(v & 0x7fffffffu));
         F<1> c[4];
 #pragma unroll
         for (int q = 0; q < 28; q++) {
@@ -1226,42 +1162,12 @@ __global__ void __launch_bounds__(64) k_msm_chunk_acc_fl2(const uint32_t* __rest
         if (!inf) {  // an infinity base is add_assign_mixed's no-op
             const F2<1> y = {c[2], c[3]};
             const F2<2> oy = (v >> 31) ? neg(y) : relax<2>(y);
-            fl2_jac_add_mixed(acc, untouched, F2<1>{c[0], c[1]}, oy);
+            fl_jac_add_mixed(acc, untouched, F2<1>{c[0], c[1]}, oy);
         }
         key = nkey;
         v = nv;
     }
-    msm_flush_fl2(cur, acc, untouched, j0, k, start, buckets, cont);
-}
-
-// k_msm_segments_fl over Fq2
-__global__ void __launch_bounds__(64) k_msm_segments_fl2(const uint64_t* __restrict__ buckets, uint32_t B, uint32_t L,
-                                                         size_t t0, size_t t1, uint64_t* __restrict__ segs) {
-    constexpr int JW = Grp<2>::JW;
-    const size_t t = t0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= t1) return;
-    const uint32_t spw = B / L;
-    const size_t w = t / spw;
-    const uint32_t j = (uint32_t)(t % spw);
-    const uint64_t* bw = buckets + (size_t)JW * (w * B);
-    FlJac2 T = fl2_jac_zero(), S = T;
-#pragma unroll 1
-    for (uint32_t m = (j + 1) * L; m > j * L; m--) {  // magnitudes (j*L, (j+1)*L], top down
-        fl2_jac_add(T, fl2_load_jac(bw + (size_t)JW * (m - 1)));
-        fl2_jac_add(S, T);
-    }
-    const uint32_t a = j * L;  // S = sum (m - a) B_m; add a * T
-    if (a && !f2_is_zero(T.z)) {
-        FlJac2 aT = T;  // top set bit of a
-        const int top = 31 - __clz(a);
-#pragma unroll 1
-        for (int bit = top - 1; bit >= 0; bit--) {
-            fl2_jac_double(aT);
-            if ((a >> bit) & 1) fl2_jac_add(aT, T);
-        }
-        fl2_jac_add(S, aT);
-    }
-    fl2_store_jac(segs + (size_t)JW * t, S);
+    msm_flush<2>(cur, acc, untouched, j0, k, start, buckets, cont);
 }
 
 // k_msm_group_sum_fl over Fq2, one lane per output
@@ -1273,14 +1179,14 @@ __global__ void __launch_bounds__(64) k_msm_group_sum_fl2(const uint64_t* __rest
     if (t >= (size_t)w1 * gpw) return;
     const size_t w = t / gpw;
     const uint32_t g = (uint32_t)(t % gpw);
-    FlJac2 acc = fl2_jac_zero();
+    FlJac2 acc = FlJac2::zero();
 #pragma unroll 1
     for (uint32_t k = 0; k < group; k++) {
         const uint32_t idx = g * group + k;
         if (idx >= count) break;
-        fl2_jac_add(acc, fl2_load_jac(in + (size_t)JW * (w * stride + idx)));
+        fl_jac_add(acc, fl_load_jac<2>(in + (size_t)JW * (w * stride + idx)));
     }
-    fl2_store_jac(out + (size_t)JW * (w * stride + g), acc);
+    fl_store_jac(out + (size_t)JW * (w * stride + g), acc);
 }
 
 // Buckets spanning more than kMsmLongSpan chunks (crowded digits: equal
@@ -1289,33 +1195,16 @@ __global__ void __launch_bounds__(64) k_msm_group_sum_fl2(const uint64_t* __rest
 // pieces, then a tree through LDS; the bucket's own piece is added last.  The
 // list comes from k_msm_bucket_fix; without long buckets the blocks exit at
 // once.  Without it one lane walked every piece (G2 at 2^18: 46 ms).
-template <int G> struct LazyJac;
-template <> struct LazyJac<1> {
-    using P = FlJac;
-    static constexpr int NT = 256;
-    static PA_DEV P zero() { return {fl_zero(), fl_one(), fl_zero()}; }
-    static PA_DEV void add(P& a, const P& b) { fl_jac_add(a, b); }
-    static PA_DEV P load(const uint64_t* p) { return fl_load_jac(p); }
-    static PA_DEV void store(uint64_t* p, const P& a) { fl_store_jac(p, a); }
-};
-template <> struct LazyJac<2> {
-    using P = FlJac2;
-    static constexpr int NT = 128;
-    static PA_DEV P zero() { return fl2_jac_zero(); }
-    static PA_DEV void add(P& a, const P& b) { fl2_jac_add(a, b); }
-    static PA_DEV P load(const uint64_t* p) { return fl2_load_jac(p); }
-    static PA_DEV void store(uint64_t* p, const P& a) { fl2_store_jac(p, a); }
-};
+template <int G> constexpr int kMsmLongFixThreads = G == 1 ? 256 : 128;
 template <int G>
-__global__ void __launch_bounds__(LazyJac<G>::NT) k_msm_long_fix(const uint32_t* __restrict__ start,
-                                                                 const uint32_t* __restrict__ end, uint32_t T,
-                                                                 const uint64_t* __restrict__ cont,
-                                                                 uint64_t* __restrict__ buckets,
-                                                                 const uint32_t* __restrict__ long_list,
-                                                                 const uint32_t* __restrict__ long_count) {
-    using L = LazyJac<G>;
-    using P = typename L::P;
-    constexpr int NT = L::NT, JW = Grp<G>::JW, PW = sizeof(P) / 4;
+__global__ void __launch_bounds__(kMsmLongFixThreads<G>) k_msm_long_fix(const uint32_t* __restrict__ start,
+                                                                        const uint32_t* __restrict__ end, uint32_t T,
+                                                                        const uint64_t* __restrict__ cont,
+                                                                        uint64_t* __restrict__ buckets,
+                                                                        const uint32_t* __restrict__ long_list,
+                                                                        const uint32_t* __restrict__ long_count) {
+    using P = FlPoint<G>;
+    constexpr int NT = kMsmLongFixThreads<G>, JW = Grp<G>::JW, PW = sizeof(P) / 4;
     __shared__ uint32_t sh[(NT / 2) * PW];
     const int t = threadIdx.x;
     const uint32_t count = *long_count;
@@ -1323,9 +1212,9 @@ __global__ void __launch_bounds__(LazyJac<G>::NT) k_msm_long_fix(const uint32_t*
     for (uint32_t idx = blockIdx.x; idx < count; idx += gridDim.x) {
         const uint32_t b = long_list[idx];
         const size_t first = start[b] / T, last = (end[b] - 1) / T;
-        P acc = L::zero();
+        P acc = P::zero();
 #pragma unroll 1
-        for (size_t k = first + 1 + t; k <= last; k += NT) L::add(acc, L::load(cont + (size_t)JW * k));
+        for (size_t k = first + 1 + t; k <= last; k += NT) fl_jac_add(acc, fl_load_jac<G>(cont + (size_t)JW * k));
 #pragma unroll 1
         for (int h = NT / 2; h >= 1; h >>= 1) {
             if (t >= h && t < 2 * h) {
@@ -1339,14 +1228,14 @@ __global__ void __launch_bounds__(LazyJac<G>::NT) k_msm_long_fix(const uint32_t*
                 uint32_t* dst = reinterpret_cast<uint32_t*>(&o);
 #pragma unroll
                 for (int q = 0; q < PW; q++) dst[q] = sh[t * PW + q];
-                L::add(acc, o);
+                fl_jac_add(acc, o);
             }
             __syncthreads();
         }
         if (t == 0) {
-            P bk = L::load(buckets + (size_t)JW * b);
-            L::add(bk, acc);
-            L::store(buckets + (size_t)JW * b, bk);
+            P bk = fl_load_jac<G>(buckets + (size_t)JW * b);
+            fl_jac_add(bk, acc);
+            fl_store_jac(buckets + (size_t)JW * b, bk);
         }
     }
 }
@@ -1436,20 +1325,21 @@ struct MsmJob {
     bool u128 = false;    // the scalar rows are 16 bytes (< 2^128): the 130-bit plan over `terms` real terms
 };
 
-// The group's kernels of steps 4-6 on the lazy core, and the lanes that
-// group_sum spends per output (G1: a quad)
+// The kernels that differ by group: the base conversions (their store loops),
+// of steps 4-6 the accumulation (G1: a two-deep prefetch) and the group sum
+// (G1: a quad per output), and the lanes that group_sum spends per output
 template <int G> struct MsmKernels;
 template <> struct MsmKernels<1> {
     static constexpr auto bases_fl = k_msm_bases_fl;
+    static constexpr auto bases_prepare = k_msm_bases_prepare;
     static constexpr auto chunk_acc = k_msm_chunk_acc_fl;
-    static constexpr auto segments = k_msm_segments_fl;
     static constexpr auto group_sum = k_msm_group_sum_fl;
     static constexpr unsigned kGroupSumLanes = 4;
 };
 template <> struct MsmKernels<2> {
     static constexpr auto bases_fl = k_msm_bases_fl2;
+    static constexpr auto bases_prepare = k_msm_bases_prepare_g2;
     static constexpr auto chunk_acc = k_msm_chunk_acc_fl2;
-    static constexpr auto segments = k_msm_segments_fl2;
     static constexpr auto group_sum = k_msm_group_sum_fl2;
     static constexpr unsigned kGroupSumLanes = 1;
 };
@@ -1585,11 +1475,11 @@ struct MsmStages {
         if ((r = hipMemsetAsync(w.long_count + q, 0, 4, st)) != hipSuccess) return r;
         hipLaunchKernelGGL(k_msm_bucket_fix<G>, dim3(msm_blocks(b1 - b0, 64)), dim3(64), 0, st, w.start, w.end, b0, b1,
                            p.T, w.cont, w.buckets, w.long_list + b0, w.long_count + q, long_span);
-        hipLaunchKernelGGL(k_msm_long_fix<G>, dim3(kMsmLongBlocks), dim3(LazyJac<G>::NT), 0, st, w.start, w.end, p.T,
-                           w.cont, w.buckets, w.long_list + b0, w.long_count + q);
+        hipLaunchKernelGGL(k_msm_long_fix<G>, dim3(kMsmLongBlocks), dim3(kMsmLongFixThreads<G>), 0, st, w.start, w.end,
+                           p.T, w.cont, w.buckets, w.long_list + b0, w.long_count + q);
         const size_t t0 = (size_t)w0 * spw, t1 = (size_t)w1 * spw;
-        hipLaunchKernelGGL(K::segments, dim3(msm_blocks(t1 - t0, 64)), dim3(64), 0, st, w.buckets, p.B, p.L, t0, t1,
-                           w.segs);
+        hipLaunchKernelGGL(k_msm_segments<G>, dim3(msm_blocks(t1 - t0, 64)), dim3(64), 0, st, w.buckets, p.B, p.L, t0,
+                           t1, w.segs);
         uint64_t *src = w.segs, *dst = w.tmp;
         for (uint32_t count = spw; count > 1;) {
             const uint32_t gpw = (count + kMsmGroup - 1) / kMsmGroup;
@@ -1818,53 +1708,25 @@ hipError_t launch_msm_u128_g1(const uint64_t* bases, const uint64_t* scalars, si
     return msm_run<1>(job, out, ws, ws_bytes, stream);
 }
 
-hipError_t launch_msm_prepare_g1(const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows, uint32_t* bad,
-                                 hipStream_t stream) {
+hipError_t launch_msm_prepare(int group, const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows,
+                              uint32_t* bad, hipStream_t stream) {
     if (n >= kMsmPreparedMax) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(bad, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess || n == 0) return e;
-    hipLaunchKernelGGL(k_msm_bases_prepare, dim3(msm_blocks(n, 256)), dim3(256), 0, stream, bases, ok, n, rows, bad);
+    const auto prepare = group == 1 ? MsmKernels<1>::bases_prepare : MsmKernels<2>::bases_prepare;
+    hipLaunchKernelGGL(prepare, dim3(msm_blocks(n, 256)), dim3(256), 0, stream, bases, ok, n, rows, bad);
     return hipGetLastError();
 }
 
-hipError_t launch_msm_prepare_g2(const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows, uint32_t* bad,
-                                 hipStream_t stream) {
-    if (n >= kMsmPreparedMax) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(bad, 0, sizeof(uint32_t), stream);
-    if (e != hipSuccess || n == 0) return e;
-    hipLaunchKernelGGL(k_msm_bases_prepare_g2, dim3(msm_blocks(n, 256)), dim3(256), 0, stream, bases, ok, n, rows,
-                       bad);
-    return hipGetLastError();
-}
-
-// k vectors over the prepared rows of either group; k = 1 without mont is the single entry's job
-template <int G>
-static hipError_t msm_prepared(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m, size_t k,
-                               bool mont, uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream) {
+// k vectors over the prepared rows of either group; k = 1 without mont is a single MSM's job
+hipError_t launch_msm_prepared(int group, const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars,
+                               size_t m, size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
+                               hipStream_t stream) {
     if (len >= kMsmPreparedMax || m > len) return hipErrorInvalidValue;
     MsmJob job{nullptr, rows, scalars, m, len, glv};
     job.vectors = k;
     job.mont = mont;
-    return msm_run<G>(job, out, ws, ws_bytes, stream);
-}
-
-hipError_t launch_msm_prepared_g1(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
-                                  uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream) {
-    return msm_prepared<1>(rows, len, glv, scalars, m, 1, false, out, ws, ws_bytes, stream);
-}
-hipError_t launch_msm_prepared_g1_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
-                                        size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
-                                        hipStream_t stream) {
-    return msm_prepared<1>(rows, len, glv, scalars, m, k, mont, out, ws, ws_bytes, stream);
-}
-hipError_t launch_msm_prepared_g2(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
-                                  uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream) {
-    return msm_prepared<2>(rows, len, glv, scalars, m, 1, false, out, ws, ws_bytes, stream);
-}
-hipError_t launch_msm_prepared_g2_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
-                                        size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
-                                        hipStream_t stream) {
-    return msm_prepared<2>(rows, len, glv, scalars, m, k, mont, out, ws, ws_bytes, stream);
+    return group == 1 ? msm_run<1>(job, out, ws, ws_bytes, stream) : msm_run<2>(job, out, ws, ws_bytes, stream);
 }
 
 hipError_t launch_scalar_mul(int group, int projective, const uint64_t* p, const uint64_t* scalars, size_t n,

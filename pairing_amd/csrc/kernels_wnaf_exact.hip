@@ -55,15 +55,8 @@
 namespace pa {
 namespace {
 
-template <int G> struct Wx;
-template <> struct Wx<1> {
-    using F = Fq;
-    static constexpr int W = 6;
-};
-template <> struct Wx<2> {
-    using F = Fq2;
-    static constexpr int W = 12;
-};
+// u64 words per coordinate of group G
+template <int G> constexpr int kWxW = Grp<G>::JW / 3;
 
 inline unsigned blocks_for(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
@@ -156,10 +149,10 @@ PA_DEV int wnaf_nonzero(const uint64_t* s, int window, int32_t* d, size_t stride
 // wnaf_exp (wnaf.rs:45-71): entry e of the table at table + 3W estride e (u64),
 // digit j at d[j dstride]
 template <int G>
-PA_DEV void wnaf_exp(Jac<typename Wx<G>::F>& r, const uint64_t* table, size_t estride, const int32_t* d,
+PA_DEV void wnaf_exp(Jac<typename Grp<G>::F>& r, const uint64_t* table, size_t estride, const int32_t* d,
                      size_t dstride, int len) {
-    using F = typename Wx<G>::F;
-    constexpr int JW = 3 * Wx<G>::W;
+    using F = typename Grp<G>::F;
+    constexpr int JW = Grp<G>::JW;
     jac_zero(r);
     bool found = false;
     for (int j = len - 1; j >= 0; j--) {
@@ -177,18 +170,10 @@ PA_DEV void wnaf_exp(Jac<typename Wx<G>::F>& r, const uint64_t* table, size_t es
     }
 }
 
-// ---------------- lazy-core helpers (G1: curve_fl.h, G2: curve_fl2.h) ----------------
+// ---------------- lazy-core table entries (the group law: curve_fl.h, curve_fl2.h) ----------------
 // table entry layout of k_wx_table_fl: x, y, z as lazy limbs, padded to 16-byte
 // pieces (G1: 42 -> 48 u32, G2: 84 -> 96 u32)
-template <int G> struct WxL;
-template <> struct WxL<1> {
-    using J = FlJac;
-    static constexpr int EW = 48;
-};
-template <> struct WxL<2> {
-    using J = FlJac2;
-    static constexpr int EW = 96;
-};
+template <int G> constexpr int kWxEntryWords = 48 * G;
 
 PA_DEV void wl_put(uint32_t* e, const F<1>& a) {
 #pragma unroll
@@ -206,18 +191,6 @@ PA_DEV void wl_get(F2<1>& a, const uint32_t* e) {
     wl_get(a.c0, e);
     wl_get(a.c1, e + 14);
 }
-PA_DEV void wl_load(F<1>& a, const uint64_t* p) { a = fl_load(p); }
-PA_DEV void wl_load(F2<1>& a, const uint64_t* p) { a = fl2_load(p); }
-PA_DEV bool wl_zero_test(const F<1>& a) { return fl_is_zero(a); }
-PA_DEV bool wl_zero_test(const F2<1>& a) { return f2_is_zero(a); }
-PA_DEV void wl_double(FlJac& p) { fl_jac_double(p); }
-PA_DEV void wl_double(FlJac2& p) { fl2_jac_double(p); }
-PA_DEV void wl_add(FlJac& s, const FlJac& o) { fl_jac_add(s, o); }
-PA_DEV void wl_add(FlJac2& s, const FlJac2& o) { fl2_jac_add(s, o); }
-PA_DEV void wl_store(uint64_t* p, const FlJac& a) { fl_store_jac(p, a); }
-PA_DEV void wl_store(uint64_t* p, const FlJac2& a) { fl2_store_jac(p, a); }
-PA_DEV void wl_set_zero(FlJac& r) { r = {fl_zero(), fl_one(), fl_zero()}; }   // ec.rs:224-230
-PA_DEV void wl_set_zero(FlJac2& r) { r = fl2_jac_zero(); }
 
 // ---------------- fixed scalar ----------------
 __global__ void __launch_bounds__(64) k_wx_scalar_digits(const uint64_t* __restrict__ scalar, int window,
@@ -232,8 +205,8 @@ __global__ void __launch_bounds__(64) k_wx_fixed_scalar(const uint64_t* __restri
                                                         const int32_t* __restrict__ digits,
                                                         const int32_t* __restrict__ len, int window,
                                                         uint64_t* __restrict__ tables, uint64_t* __restrict__ out) {
-    using F = typename Wx<G>::F;
-    constexpr int JW = 3 * Wx<G>::W;
+    using F = typename Grp<G>::F;
+    constexpr int JW = Grp<G>::JW;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     // wnaf_table (wnaf.rs:3-15)
@@ -284,8 +257,8 @@ PA_DEV bool jac_on_curve(const Jac<F>& p) {
 // nonzero point is nonzero -- the multiply then tests for zero only after adds
 template <int G>
 __global__ void __launch_bounds__(64) k_wx_prep(const uint64_t* __restrict__ base, uint64_t* __restrict__ meta) {
-    using F = typename Wx<G>::F;
-    constexpr int W = Wx<G>::W;
+    using F = typename Grp<G>::F;
+    constexpr int W = kWxW<G>;
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     Jac<F> b, d;
     load_jac(b, base);
@@ -327,24 +300,19 @@ PA_DEV bool wl_inverse(F2<1>& r, const F2<1>& a) {   // fq2.rs:138-155
     r = {mul(a.c0, t), mul(red(neg(a.c1)), t)};
     return ok;
 }
-PA_DEV void wl_store1(uint64_t* p, const F<1>& a) { fl_store(p, a); }
-PA_DEV void wl_store1(uint64_t* p, const F2<1>& a) { fl2_store(p, a); }
-PA_DEV FlJac wl_load_jac(const uint64_t* p, FlJac*) { return fl_load_jac(p); }
-PA_DEV FlJac2 wl_load_jac(const uint64_t* p, FlJac2*) { return fl2_load_jac(p); }
 
 template <int G>
 __global__ void __launch_bounds__(64) k_wx_affine_fl(const uint64_t* __restrict__ base, size_t N,
                                                      uint64_t* __restrict__ aff, uint64_t* __restrict__ meta) {
-    constexpr int W = Wx<G>::W;
-    using J = typename WxL<G>::J;
+    constexpr int W = kWxW<G>;
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= N || meta[5 * W]) return;   // a zero B or D: the serial chain runs instead
-    const J b = wl_load_jac(base, (J*)nullptr);
-    J r = b;
+    const FlPoint<G> b = fl_load_jac<G>(base);
+    FlPoint<G> r = b;
     const uint64_t m = 2 * (uint64_t)k + 1;
     for (int bit = 62 - __builtin_clzll(m); bit >= 0; bit--) {
-        if (!wl_zero_test(r.z)) wl_double(r);
-        if ((m >> bit) & 1) wl_add(r, b);
+        if (!fl_is_zero(r.z)) fl_jac_double(r);
+        if ((m >> bit) & 1) fl_jac_add(r, b);
     }
     decltype(r.z) zi;
     if (!wl_inverse(zi, r.z)) {   // (2k + 1) B = 0: B has small order
@@ -352,15 +320,15 @@ __global__ void __launch_bounds__(64) k_wx_affine_fl(const uint64_t* __restrict_
         return;
     }
     const auto zi2 = sqr(zi);
-    wl_store1(aff + (size_t)2 * W * k, mul(r.x, zi2));
-    wl_store1(aff + (size_t)2 * W * k + W, mul(r.y, mul(zi2, zi)));
+    fl_store(aff + (size_t)2 * W * k, mul(r.x, zi2));
+    fl_store(aff + (size_t)2 * W * k + W, mul(r.y, mul(zi2, zi)));
 }
 
 template <int G>
 __global__ void __launch_bounds__(64) k_wx_coef(const uint64_t* __restrict__ base, const uint64_t* __restrict__ aff,
                                                 size_t N, uint64_t* __restrict__ coef, uint64_t* __restrict__ meta) {
-    using F = typename Wx<G>::F;
-    constexpr int W = Wx<G>::W;
+    using F = typename Grp<G>::F;
+    constexpr int W = kWxW<G>;
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= N || meta[5 * W]) return;
     F c;
@@ -524,15 +492,15 @@ __global__ void __launch_bounds__(64) k_wx_scan_fl2(const uint64_t* __restrict__
             started = true;
         }
     }
-    fl2_store(cout + 12 * i, mul(fl2_load(cin + 12 * i), r));
+    fl_store(cout + 12 * i, mul(fl2_load(cin + 12 * i), r));
 }
 
 template <int G>
 __global__ void __launch_bounds__(64) k_wx_finish(const uint64_t* __restrict__ base, const uint64_t* __restrict__ aff,
                                                   const uint64_t* __restrict__ zs, size_t N,
                                                   uint64_t* __restrict__ table, const uint64_t* __restrict__ meta) {
-    using F = typename Wx<G>::F;
-    constexpr int W = Wx<G>::W;
+    using F = typename Grp<G>::F;
+    constexpr int W = kWxW<G>;
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= N || meta[5 * W]) return;
     uint64_t* t = table + (size_t)3 * W * k;
@@ -557,8 +525,8 @@ __global__ void __launch_bounds__(64) k_wx_finish(const uint64_t* __restrict__ b
 template <int G>
 __global__ void __launch_bounds__(64) k_wx_serial(const uint64_t* __restrict__ base, size_t N,
                                                   uint64_t* __restrict__ table, const uint64_t* __restrict__ meta) {
-    using F = typename Wx<G>::F;
-    constexpr int W = Wx<G>::W;
+    using F = typename Grp<G>::F;
+    constexpr int W = kWxW<G>;
     if (blockIdx.x != 0 || threadIdx.x != 0 || !meta[5 * W]) return;
     Jac<F> b, d;
     load_jac(b, base);
@@ -574,13 +542,10 @@ __global__ void __launch_bounds__(64) k_wx_serial(const uint64_t* __restrict__ b
 template <int G>
 __global__ void __launch_bounds__(64) k_wx_table_fl(const uint64_t* __restrict__ table, size_t N,
                                                     uint32_t* __restrict__ tfl) {
-    constexpr int W = Wx<G>::W, EW = WxL<G>::EW, L = 14 * (W / 6);
+    constexpr int EW = kWxEntryWords<G>, L = 14 * G;
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= N) return;
-    typename WxL<G>::J t;
-    wl_load(t.x, table + (size_t)3 * W * k);
-    wl_load(t.y, table + (size_t)3 * W * k + W);
-    wl_load(t.z, table + (size_t)3 * W * k + 2 * W);
+    const FlPoint<G> t = fl_load_jac<G>(table + (size_t)Grp<G>::JW * k);
     uint32_t e[EW];
     wl_put(e, t.x);
     wl_put(e + L, t.y);
@@ -593,8 +558,8 @@ __global__ void __launch_bounds__(64) k_wx_table_fl(const uint64_t* __restrict__
 }
 
 template <int G>
-PA_DEV typename WxL<G>::J wl_entry(const uint32_t* __restrict__ tfl, int e) {
-    constexpr int EW = WxL<G>::EW, L = 14 * G;
+PA_DEV FlPoint<G> wl_entry(const uint32_t* __restrict__ tfl, int e) {
+    constexpr int EW = kWxEntryWords<G>, L = 14 * G;
     const uint4* src = reinterpret_cast<const uint4*>(tfl + (size_t)EW * e);
     uint32_t v[EW];
 #pragma unroll
@@ -605,7 +570,7 @@ PA_DEV typename WxL<G>::J wl_entry(const uint32_t* __restrict__ tfl, int e) {
         v[4 * j + 2] = x.z;
         v[4 * j + 3] = x.w;
     }
-    typename WxL<G>::J t;
+    FlPoint<G> t;
     wl_get(t.x, v);
     wl_get(t.y, v + L);
     wl_get(t.z, v + 2 * L);
@@ -626,8 +591,8 @@ __global__ void __launch_bounds__(64, G == 1 ? 2 : 1) k_wx_fixed_base_mul_fl(con
                                                              const uint32_t* __restrict__ perm,
                                                              const int32_t* __restrict__ cnts,
                                                              uint64_t* __restrict__ out) {
-    constexpr int W = Wx<G>::W, JW = 3 * W;
-    using J = typename WxL<G>::J;
+    constexpr int W = kWxW<G>, JW = Grp<G>::JW;
+    using J = FlPoint<G>;
     const size_t t_ = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t_ >= n) return;
     const bool on_curve = meta[5 * W + 1] != 0;
@@ -636,16 +601,15 @@ __global__ void __launch_bounds__(64, G == 1 ? 2 : 1) k_wx_fixed_base_mul_fl(con
     const size_t i = perm ? perm[t_] : t_;
     int32_t* d = digits + i;
     const int cnt = perm ? cnts[i] : wnaf_nonzero(scalars + 4 * i, window, d, n);
-    J r;
-    wl_set_zero(r);
+    J r = J::zero();
     bool rz = true;   // r is zero (z == 0)
     auto doublings = [&](int m) {
         if (on_curve) {
             if (!rz)
-                for (int j = m; j > 0; j--) wl_double(r);
+                for (int j = m; j > 0; j--) fl_jac_double(r);
         } else {
             for (int j = m; j > 0; j--)
-                if (!wl_zero_test(r.z)) wl_double(r);
+                if (!fl_is_zero(r.z)) fl_jac_double(r);
         }
     };
     int prev = -1;
@@ -654,13 +618,13 @@ __global__ void __launch_bounds__(64, G == 1 ? 2 : 1) k_wx_fixed_base_mul_fl(con
         const int pos = pk & 511, v = pk >> 9;
         if (prev >= 0) doublings(prev - pos);
         J t = wl_entry<G>(tfl, (v > 0 ? v : -v) >> 1);
-        if (v < 0 && !wl_zero_test(t.z)) t.y = red(neg(t.y));
-        wl_add(r, t);
-        rz = wl_zero_test(r.z);
+        if (v < 0 && !fl_is_zero(t.z)) t.y = red(neg(t.y));
+        fl_jac_add(r, t);
+        rz = fl_is_zero(r.z);
         prev = pos;
     }
     if (prev > 0) doublings(prev);
-    wl_store(out + (size_t)JW * i, r);
+    fl_store_jac(out + (size_t)JW * i, r);
 }
 
 // Lanes of a wave run the wnaf_exp rounds of their scalars in lockstep: each
@@ -779,7 +743,7 @@ WxLayout wx_layout(int group, size_t n, int window) {
     L.digits = at;
     at = align256(at + 4 * (size_t)wx_max_nonzero(window) * n);
     L.tfl = at;
-    at = align256(at + 4 * (size_t)(group == 1 ? WxL<1>::EW : WxL<2>::EW) * N);
+    at = align256(at + 4 * (size_t)(group == 1 ? kWxEntryWords<1> : kWxEntryWords<2>) * N);
     // the scalar order of the multiply: keys and indices in and out of the sort
     L.keys = at;
     at = align256(at + 2 * 8 * n);

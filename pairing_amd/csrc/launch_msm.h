@@ -38,19 +38,14 @@ constexpr size_t kMsmPreparedMax = (size_t)1 << 30;
 size_t msm_prepared_rows_bytes(size_t n, int group = 1);
 // rows from the affine records; *bad = number of i with ok[i] == 0 (the
 // membership flags of launch_subgroup_check over the same records)
-hipError_t launch_msm_prepare_g1(const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows, uint32_t* bad,
-                                 hipStream_t stream);
-hipError_t launch_msm_prepare_g2(const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows, uint32_t* bad,
-                                 hipStream_t stream);
+hipError_t launch_msm_prepare(int group, const uint64_t* bases, const uint8_t* ok, size_t n, uint32_t* rows,
+                              uint32_t* bad, hipStream_t stream);
 // out[0] = sum_{i < m} scalars[i] * P_i over the rows of `len` prepared bases.
+// (launch_msm_prepared with k = 1, mont = false.)
 // glv (every base in the subgroup): s = q x^2 + rem, the two halves over rows i
 // and len + i in ceil(130 / c) windows; otherwise the 257-bit pipeline over rows
 // [0, m).  `ws` holds msm_prepared_workspace_bytes(m, glv, group) bytes.
 size_t msm_prepared_workspace_bytes(size_t m, bool glv, int group = 1);
-hipError_t launch_msm_prepared_g1(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
-                                  uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream);
-hipError_t launch_msm_prepared_g2(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
-                                  uint64_t* out, void* ws, size_t ws_bytes, hipStream_t stream);
 
 // out[j] = sum_{i < m} scalars[j m + i] * P_i for j < k: k vectors end to end
 // through one pipeline of k W windows.  mont: the rows are Montgomery Fr below
@@ -60,11 +55,8 @@ hipError_t launch_msm_prepared_g2(const uint32_t* rows, size_t len, bool glv, co
 // workspace size 0 and is refused.
 bool msm_prepared_batch_fits(size_t m, size_t k, bool glv, int group = 1);
 size_t msm_prepared_batch_workspace_bytes(size_t m, size_t k, bool glv, int group = 1);
-hipError_t launch_msm_prepared_g1_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
-                                        size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
-                                        hipStream_t stream);
-hipError_t launch_msm_prepared_g2_batch(const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars, size_t m,
-                                        size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
-                                        hipStream_t stream);
+hipError_t launch_msm_prepared(int group, const uint32_t* rows, size_t len, bool glv, const uint64_t* scalars,
+                               size_t m, size_t k, bool mont, uint64_t* out, void* ws, size_t ws_bytes,
+                               hipStream_t stream);
 
 }  // namespace pa

@@ -324,9 +324,9 @@ extern "C" __global__ void __launch_bounds__(64) fl_unit_tower(const uint32_t* _
 //  op 0 fl_jac_double      s (3 slots)
 //     1 fl_jac_add_mixed   s, ox (F<1>), oy (F<2>), word 0 of slot 5 = untouched; flag = untouched after
 //     2 fl_jac_add         s, o
-//     3 fl2_jac_double     s (6 slots)
-//     4 fl2_jac_add_mixed  s, ox (2 slots), oy (F2<2>), word 0 of slot 10 = untouched
-//     5 fl2_jac_add        s, o
+//     3 fl_jac_double      s (6 slots), over Fq2
+//     4 fl_jac_add_mixed   s, ox (2 slots), oy (F2<2>), word 0 of slot 10 = untouched
+//     5 fl_jac_add         s, o
 //  (the quad forms fl_jac_add_q / fl_jac_double_q: fl_unit_curve_quad below)
 extern "C" __global__ void __launch_bounds__(64) fl_unit_curve(const uint32_t* __restrict__ in,
                                                                uint32_t* __restrict__ out, uint32_t n, uint32_t op,
@@ -356,14 +356,14 @@ extern "C" __global__ void __launch_bounds__(64) fl_unit_curve(const uint32_t* _
         FlJac2 s = {ld2<1>(x, 0), ld2<1>(x, 2), ld2<1>(x, 4)};
         uint32_t flag = 0;
         if (op == 3) {
-            fl2_jac_double(s);
+            fl_jac_double(s);
         } else if (op == 4) {
             bool untouched = x[16 * 10] != 0;
-            fl2_jac_add_mixed(s, untouched, ld2<1>(x, 6), ld2<2>(x, 8));
+            fl_jac_add_mixed(s, untouched, ld2<1>(x, 6), ld2<2>(x, 8));
             flag = untouched ? 1u : 0u;
         } else {
             const FlJac2 o = {ld2<1>(x, 6), ld2<1>(x, 8), ld2<1>(x, 10)};
-            fl2_jac_add(s, o);
+            fl_jac_add(s, o);
         }
         st2(y, 0, s.x, flag);
         st2(y, 2, s.y, flag);
