@@ -693,6 +693,107 @@ int pa_groth16_prove(const pa_groth16_pk *pk, const pa_r1cs *r1cs, const pa_fr_n
                      const pa_fr *host_witness, const pa_fr *host_r, const pa_fr *host_s, size_t k,
                      pa_groth16_proof *proofs);   /* host memory */
 
+/* ---- Groth16 parameter generation: trapdoor in, keys out ----
+ * bellman's generate_parameters for a trapdoor (tau, alpha, beta, gamma, delta)
+ * that the caller sampled, over base points g1 and g2.  With n = 2^log_n the
+ * domain's size, L_j(tau) its Lagrange coefficients at tau, variable i in
+ * [0, n_vars) and n_public counting the constant one:
+ *   u_i = sum_j A[j][i] L_j(tau)   v_i = sum_j B[j][i] L_j(tau)   w_i = sum_j C[j][i] L_j(tau)
+ *   mix_i = (beta u_i + alpha v_i + w_i) / gamma   for i <  n_public   (ic[i])
+ *   mix_i = (beta u_i + alpha v_i + w_i) / delta   for i >= n_public   (l_query[i - n_public])
+ *   h_i   = tau^i (tau^n - 1) / delta              for i <  n - 1      (h_query, h_len = n - 1)
+ *   a_query[i] = u_i g1   b_g1_query[i] = v_i g1   b_g2_query[i] = v_i g2
+ *   alpha_g1, beta_g1, delta_g1 = alpha g1, beta g1, delta g1
+ *   beta_g2, gamma_g2, delta_g2 = beta g2, gamma g2, delta g2
+ * L is the inverse transform of the powers 1, tau, .., tau^(n-1), L_j = n^-1
+ * sum_i tau^i w^(-ij): no inversion, right for every tau (tau = w^m gives L_m = 1,
+ * the other L_j = 0 and every h_i = 0; tau = 0 gives L_j = n^-1).  The outputs
+ * are the affine records pa_g{1,2}_into_affine_batch write, so they are
+ * bit-exact; a zero scalar gives the record of the point at infinity, e.g.
+ * a_query[i] for a variable that occurs in no row of A.  The query arrays stay
+ * dense (bellman's filtering of zero points and its density trackers are not
+ * reproduced).  The matrices are taken as given: bellman's extra rows
+ * input_i * 0 = 0 are the caller's to include.  g1 and g2 may be any on-curve
+ * points, infinity included; off-curve bases are undefined.
+ *
+ * pa_groth16_circuit holds the transposed matrices (rows = variables, columns =
+ * constraints) as a pa_r1cs image on the device current at creation, so a
+ * variable of thousands of occurrences (the constant one) is a row of many
+ * chunks there.  Creation errors are those of pa_r1cs_create, plus n_public >
+ * n_cols and n_cols > 2^PA_NTT_MAX_LOG_N.  Lifetime rules as for pa_r1cs.
+ *
+ * Output layout (pa_groth16_generate_offsets returns it; a pa_groth16_key and a
+ * pa_groth16_vkey can point straight into the arrays):
+ *   g1_out = a_query (n_vars) | b_g1_query (n_vars) | ic (n_public) | l_query (n_vars - n_public)
+ *            | h_query (n - 1) | alpha_g1 | beta_g1 | delta_g1          3 n_vars + n + 2 records
+ *   g2_out = b_g2_query (n_vars) | beta_g2 | gamma_g2 | delta_g2       n_vars + 3 records
+ * pa_groth16_generate_scalars* write the discrete logarithms of g1_out in the
+ * same order as Montgomery rows (the last three are alpha, beta, delta): the Fr
+ * half of the call without any curve arithmetic.
+ *
+ * The trapdoor is host memory in every entry (160 bytes; it travels as kernel
+ * arguments).  The device entries take device pointers, run in stream order on
+ * `stream` (the G1 multiply orders its side streams with events, as
+ * pa_g1_wnaf_fixed_base_device does), allocate nothing and read nothing back:
+ * a powers kernel, pa_fr_ntt_device (inverse), the chunked product of the
+ * transposed image with L, a scalar kernel, one pa_g1_wnaf_fixed_base_device
+ * and one pa_g2_wnaf_fixed_base_device over the whole vectors, the two batch
+ * normalizations and a pack kernel each.  workspace:
+ * pa_groth16_generate_workspace_bytes(circuit, log_n) bytes for either device
+ * entry (0 for a NULL circuit or 2^log_n < rows).  Errors, all
+ * PA_ERR_INVALID_ARGUMENT before anything runs: a NULL pointer, 2^log_n < rows
+ * (log_n is the domain's), a trapdoor value >= r, gamma = 0 or delta = 0
+ * (bellman's UnexpectedIdentity), circuit, domain and stream on different
+ * devices, a workspace that is too small. */
+typedef struct pa_groth16_circuit pa_groth16_circuit;
+typedef struct { pa_fr tau, alpha, beta, gamma, delta; } pa_groth16_trapdoor;   /* host memory, Montgomery, < r */
+typedef struct {
+    size_t a_query, b_g1_query, ic, l_query, h_query, alpha_g1, beta_g1, delta_g1, g1_len;   /* records into g1_out */
+    size_t b_g2_query, beta_g2, gamma_g2, delta_g2, g2_len;                                  /* records into g2_out */
+    size_t h_len;                                                                            /* n - 1 */
+} pa_groth16_generate_layout;
+static inline pa_groth16_generate_layout pa_groth16_generate_offsets(size_t n_vars, size_t n_public, unsigned log_n) {
+    pa_groth16_generate_layout o;
+    o.h_len = ((size_t)1 << log_n) - 1;
+    o.a_query = 0;
+    o.b_g1_query = n_vars;
+    o.ic = 2 * n_vars;
+    o.l_query = 2 * n_vars + n_public;
+    o.h_query = 3 * n_vars;
+    o.alpha_g1 = o.h_query + o.h_len;
+    o.beta_g1 = o.alpha_g1 + 1;
+    o.delta_g1 = o.alpha_g1 + 2;
+    o.g1_len = o.alpha_g1 + 3;
+    o.b_g2_query = 0;
+    o.beta_g2 = n_vars;
+    o.gamma_g2 = n_vars + 1;
+    o.delta_g2 = n_vars + 2;
+    o.g2_len = n_vars + 3;
+    return o;
+}
+int pa_groth16_circuit_create(const pa_fr_csr *a, const pa_fr_csr *b, const pa_fr_csr *c, size_t n_rows, size_t n_cols,
+                              size_t n_public, pa_groth16_circuit **out);
+void pa_groth16_circuit_free(pa_groth16_circuit *circuit);   /* NULL is a no-op */
+size_t pa_groth16_circuit_rows(const pa_groth16_circuit *circuit);
+size_t pa_groth16_circuit_cols(const pa_groth16_circuit *circuit);       /* n_vars */
+size_t pa_groth16_circuit_n_public(const pa_groth16_circuit *circuit);
+size_t pa_groth16_circuit_bytes(const pa_groth16_circuit *circuit);      /* device memory it holds */
+size_t pa_groth16_generate_g1_len(const pa_groth16_circuit *circuit, unsigned log_n);   /* 3 n_vars + n + 2 */
+size_t pa_groth16_generate_g2_len(const pa_groth16_circuit *circuit);                   /* n_vars + 3 */
+size_t pa_groth16_generate_workspace_bytes(const pa_groth16_circuit *circuit, unsigned log_n);
+int pa_groth16_generate_device(const pa_groth16_circuit *circuit, const pa_fr_ntt_domain *d,
+                               const pa_g1_affine *dev_g1, const pa_g2_affine *dev_g2,
+                               const pa_groth16_trapdoor *host_trapdoor, pa_g1_affine *dev_g1_out,
+                               pa_g2_affine *dev_g2_out, void *workspace, size_t workspace_bytes, void *stream);
+int pa_groth16_generate(const pa_groth16_circuit *circuit, const pa_fr_ntt_domain *d, const pa_g1_affine *g1,
+                        const pa_g2_affine *g2, const pa_groth16_trapdoor *trapdoor, pa_g1_affine *g1_out,
+                        pa_g2_affine *g2_out);   /* host memory */
+int pa_groth16_generate_scalars_device(const pa_groth16_circuit *circuit, const pa_fr_ntt_domain *d,
+                                       const pa_groth16_trapdoor *host_trapdoor, pa_fr *dev_out, void *workspace,
+                                       size_t workspace_bytes, void *stream);
+int pa_groth16_generate_scalars(const pa_groth16_circuit *circuit, const pa_fr_ntt_domain *d,
+                                const pa_groth16_trapdoor *trapdoor, pa_fr *out);   /* host memory */
+
 /* ---- Groth16 verifier: k proofs per call over a prepared verifying key ----
  * bellman's prepare_verifying_key and verify_proof.  For proof j with public
  * inputs x_1 .. x_l, l = n_public - 1 (n_public counts the constant one, as in

@@ -821,6 +821,111 @@ private:
     FrNttDomain domain_;
 };
 
+// The constraint system as parameter generation reads it (pa_groth16_circuit):
+// the transposed matrices on the device.  n_public counts the constant one.
+// Move-only; the destructor frees the device memory.
+class Groth16Circuit {
+public:
+    Groth16Circuit(const R1cs::Csr& a, const R1cs::Csr& b, const R1cs::Csr& c, size_t n_rows, size_t n_cols,
+                   size_t n_public) {
+        const R1cs::Csr* ms[3] = {&a, &b, &c};
+        pa_fr_csr raw[3];
+        for (int i = 0; i < 3; i++) {
+            if (ms[i]->row_ptr.size() != n_rows + 1 || ms[i]->col.size() != ms[i]->val.size() ||
+                ms[i]->row_ptr.back() != ms[i]->col.size())
+                throw std::invalid_argument("Groth16Circuit: row_ptr, col and val do not describe n_rows rows");
+            raw[i] = {ms[i]->row_ptr.data(), ms[i]->col.data(), ms[i]->val.data()};
+        }
+        check(pa_groth16_circuit_create(&raw[0], &raw[1], &raw[2], n_rows, n_cols, n_public, &h_), "Groth16Circuit");
+    }
+    Groth16Circuit(const Groth16Circuit&) = delete;
+    Groth16Circuit& operator=(const Groth16Circuit&) = delete;
+    Groth16Circuit(Groth16Circuit&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Groth16Circuit& operator=(Groth16Circuit&& o) noexcept {
+        if (this != &o) {
+            pa_groth16_circuit_free(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~Groth16Circuit() { pa_groth16_circuit_free(h_); }
+
+    size_t rows() const { return pa_groth16_circuit_rows(h_); }
+    size_t cols() const { return pa_groth16_circuit_cols(h_); }
+    size_t n_public() const { return pa_groth16_circuit_n_public(h_); }
+    const pa_groth16_circuit* get() const { return h_; }
+
+private:
+    pa_groth16_circuit* h_ = nullptr;
+};
+
+// What generate_parameters returns: the arrays of the proving and the verifying
+// key as affine records.  key() and vkey() are views into this object's
+// vectors: they are valid while it lives and is not modified.
+struct Groth16Params {
+    std::vector<pa_g1_affine> a_query, b_g1_query, l_query, h_query, ic;
+    std::vector<pa_g2_affine> b_g2_query;
+    pa_g1_affine alpha_g1, beta_g1, delta_g1;
+    pa_g2_affine beta_g2, gamma_g2, delta_g2;
+    size_t n_public = 0;
+
+    pa_groth16_key key() const {
+        pa_groth16_key k;
+        k.alpha_g1 = alpha_g1;
+        k.beta_g1 = beta_g1;
+        k.delta_g1 = delta_g1;
+        k.beta_g2 = beta_g2;
+        k.delta_g2 = delta_g2;
+        k.n_vars = a_query.size();
+        k.n_public = n_public;
+        k.a_query = a_query.data();
+        k.b_g1_query = b_g1_query.data();
+        k.b_g2_query = b_g2_query.data();
+        k.l_query = l_query.data();
+        k.h_query = h_query.data();
+        k.h_len = h_query.size();
+        return k;
+    }
+    pa_groth16_vkey vkey() const {
+        pa_groth16_vkey k;
+        k.alpha_g1 = alpha_g1;
+        k.beta_g2 = beta_g2;
+        k.gamma_g2 = gamma_g2;
+        k.delta_g2 = delta_g2;
+        k.ic = ic.data();
+        k.n_public = ic.size();
+        return k;
+    }
+};
+
+// bellman's generate_parameters for a trapdoor the caller sampled (pa_groth16_generate):
+// the domain must hold the circuit's rows; g1 and g2 are the base points.
+inline Groth16Params generate_parameters(const Groth16Circuit& circuit, const FrNttDomain& domain,
+                                         const pa_g1_affine& g1, const pa_g2_affine& g2,
+                                         const pa_groth16_trapdoor& trapdoor) {
+    const pa_groth16_generate_layout o = pa_groth16_generate_offsets(circuit.cols(), circuit.n_public(), domain.log_n());
+    std::vector<pa_g1_affine> p1(o.g1_len);
+    std::vector<pa_g2_affine> p2(o.g2_len);
+    check(pa_groth16_generate(circuit.get(), domain.get(), &g1, &g2, &trapdoor, p1.data(), p2.data()),
+          "generate_parameters");
+    Groth16Params r;
+    r.n_public = circuit.n_public();
+    r.a_query.assign(p1.begin() + o.a_query, p1.begin() + o.b_g1_query);
+    r.b_g1_query.assign(p1.begin() + o.b_g1_query, p1.begin() + o.ic);
+    r.ic.assign(p1.begin() + o.ic, p1.begin() + o.l_query);
+    r.l_query.assign(p1.begin() + o.l_query, p1.begin() + o.h_query);
+    r.h_query.assign(p1.begin() + o.h_query, p1.begin() + o.alpha_g1);
+    r.alpha_g1 = p1[o.alpha_g1];
+    r.beta_g1 = p1[o.beta_g1];
+    r.delta_g1 = p1[o.delta_g1];
+    r.b_g2_query.assign(p2.begin(), p2.begin() + o.beta_g2);
+    r.beta_g2 = p2[o.beta_g2];
+    r.gamma_g2 = p2[o.gamma_g2];
+    r.delta_g2 = p2[o.delta_g2];
+    return r;
+}
+
 // A Groth16 verifier: the verifying key prepared on the device (pa_groth16_vk).
 // verify() checks k proofs in one call; the inputs are k vectors of n_inputs()
 // rows end to end, Montgomery (the witness format) unless montgomery = false.

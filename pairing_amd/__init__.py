@@ -18,7 +18,7 @@ import numpy as np
 
 from ._native import (W_FQ, W_FQ2, W_FQ6, W_FQ12, W_FR, W_G1A, W_G1, W_G2A, W_G2, W_G2P, NTT_MAX_LOG_N, FrNttDomain, G1MsmBases, G2MsmBases,
                       FrCsr, Groth16Key, Groth16Pk, Groth16VKey, Groth16Vk, GROTH16_VK_MAX_INPUTS, GROTH16_ENCODED_PROOF_BYTES,
-                      R1cs, R1CS_CHUNK_LEN, W_PROOF,
+                      R1cs, R1CS_CHUNK_LEN, W_PROOF, Groth16Circuit, Groth16Params, trapdoor_rows,
                       PairingError, _lib, as_rows, batch_shape, call, csr_offsets, device_count, msm_bases, msm_scalars, ntt_mode, ptr, set_decode_kernel, set_device, set_pairing_kernel, version)
 
 __all__ = [
@@ -41,6 +41,7 @@ __all__ = [
     "R1cs", "r1cs", "r1cs_eval", "R1CS_CHUNK_LEN", "Groth16Pk", "groth16_pk", "groth16_prove",
     "Groth16Vk", "groth16_vk", "groth16_verify", "groth16_verify_encoded", "groth16_input_sum",
     "groth16_verify_aggregate", "groth16_verify_aggregate_encoded", "groth16_aggregate_points", "g1_multiexp_u128",
+    "Groth16Circuit", "Groth16Params", "groth16_circuit", "groth16_generate", "groth16_generate_scalars",
     "g1_eq", "g2_eq", "g1_double", "g2_double", "g1_add", "g2_add", "g1_add_mixed", "g2_add_mixed", "g1_negate", "g2_negate",
     "g1_sub", "g2_sub", "g1_into_affine", "g2_into_affine", "g1_into_projective", "g2_into_projective",
     "g2_batch_normalization", "g2_wnaf_fixed_base",
@@ -871,6 +872,55 @@ def groth16_prove(pk, system, domain, witness, r, s):
     out = np.zeros((k, W_PROOF), np.uint64)
     if k:
         call("pa_groth16_prove", h, hr, hd, ptr(w), ptr(r), ptr(s), k, ptr(out))
+    return out
+
+
+def groth16_circuit(a, b, c, n_rows, n_cols, n_public):
+    """The constraint system as parameter generation reads it, on the current device
+    (pa_groth16_circuit_create): a, b, c CSR triples as r1cs() takes them, n_cols variables of
+    which the first n_public (counting the constant one) are public.  Returns a Groth16Circuit
+    (rows, cols, n_public, bytes, close())."""
+    import ctypes
+    n_rows, n_cols, n_public = int(n_rows), int(n_cols), int(n_public)
+    if n_rows < 0 or n_cols < 0 or n_rows > 1 << NTT_MAX_LOG_N or n_cols > 1 << NTT_MAX_LOG_N:
+        raise ValueError("n_rows and n_cols must be 0..2^%d" % NTT_MAX_LOG_N)
+    if n_public < 0 or n_public > n_cols:
+        raise ValueError("n_public must be 0..n_cols = %d, got %d" % (n_cols, n_public))
+    ms = [_csr(m, n_rows, n_cols, name) for m, name in ((a, "a"), (b, "b"), (c, "c"))]
+    h = ctypes.c_void_p(0)
+    call("pa_groth16_circuit_create", *(ctypes.byref(m[0]) for m in ms), n_rows, n_cols, n_public, ctypes.byref(h))
+    return Groth16Circuit._adopt(h)
+
+
+def groth16_generate(circuit, domain, trapdoor, g1, g2):
+    """bellman's generate_parameters for the given trapdoor (pa_groth16_generate): trapdoor
+    (5, 4) Montgomery Fr rows tau, alpha, beta, gamma, delta (below r; gamma, delta not zero),
+    g1 (1, 13) and g2 (1, 25) affine base points.  Returns a Groth16Params: the named arrays of
+    the proving and the verifying key as affine records, bit for bit what into_affine gives for
+    them, with pk_args() for groth16_pk and vk_args() for groth16_vk."""
+    if not isinstance(circuit, Groth16Circuit):
+        raise ValueError("circuit must come from groth16_circuit")
+    (h, hd), log_n = circuit.check_generate(domain)
+    t = trapdoor_rows(trapdoor)
+    p1, p2 = as_rows(g1, W_G1A, "g1"), as_rows(g2, W_G2A, "g2")
+    if p1.shape[0] != 1 or p2.shape[0] != 1:
+        raise ValueError("g1 and g2 must be one affine record each, got %d and %d" % (p1.shape[0], p2.shape[0]))
+    o1 = np.zeros((circuit.g1_len(log_n), W_G1A), np.uint64)
+    o2 = np.zeros((circuit.g2_len(), W_G2A), np.uint64)
+    call("pa_groth16_generate", h, hd, ptr(p1), ptr(p2), ptr(t), ptr(o1), ptr(o2))
+    return Groth16Params(o1, o2, circuit.cols, circuit.n_public, log_n)
+
+
+def groth16_generate_scalars(circuit, domain, trapdoor):
+    """The discrete logarithms of groth16_generate's G1 array in the same order, as
+    (3 n_vars + 2^log_n + 2, 4) Montgomery Fr rows: u, v, the mixed rows (ic then l_query), the
+    h rows, then alpha, beta, delta (pa_groth16_generate_scalars)."""
+    if not isinstance(circuit, Groth16Circuit):
+        raise ValueError("circuit must come from groth16_circuit")
+    (h, hd), log_n = circuit.check_generate(domain)
+    t = trapdoor_rows(trapdoor)
+    out = np.zeros((circuit.g1_len(log_n), W_FR), np.uint64)
+    call("pa_groth16_generate_scalars", h, hd, ptr(t), ptr(out))
     return out
 
 

@@ -251,6 +251,18 @@ _SIGS.update({
     "pa_groth16_verify_aggregate_encoded": [_P, _P, _P, _N, ctypes.c_uint, _P, _N, _P, _P, _P],
     "pa_groth16_verify_aggregate_points_device": [_P, _P, _P, _N, ctypes.c_uint, _P, _N, _P, _P, _N, _P],
     "pa_groth16_verify_aggregate_points": [_P, _P, _P, _N, ctypes.c_uint, _P, _N, _P],
+    "pa_groth16_circuit_create": [_P, _P, _P, _N, _N, _N, ctypes.POINTER(_P)],
+    "pa_groth16_circuit_rows": [_P],                    # these seven return size_t (below)
+    "pa_groth16_circuit_cols": [_P],
+    "pa_groth16_circuit_n_public": [_P],
+    "pa_groth16_circuit_bytes": [_P],
+    "pa_groth16_generate_g1_len": [_P, ctypes.c_uint],
+    "pa_groth16_generate_g2_len": [_P],
+    "pa_groth16_generate_workspace_bytes": [_P, ctypes.c_uint],
+    "pa_groth16_generate_device": [_P, _P, _P, _P, _P, _P, _P, _P, _N, _P],
+    "pa_groth16_generate": [_P, _P, _P, _P, _P, _P, _P],
+    "pa_groth16_generate_scalars_device": [_P, _P, _P, _P, _P, _N, _P],
+    "pa_groth16_generate_scalars": [_P, _P, _P, _P],
 })
 for _name, _args in _SIGS.items():
     _fn = getattr(_lib, _name)
@@ -279,10 +291,13 @@ for _name in ("pa_fr_ntt_domain_bytes", "pa_fr_ntt_polys_per_workgroup", "pa_fr_
 for _name in ("pa_r1cs_rows", "pa_r1cs_cols", "pa_r1cs_bytes", "pa_r1cs_eval_workspace_bytes", "pa_r1cs_chunk_len",
               "pa_groth16_prove_workspace_bytes", "pa_groth16_vk_n_public", "pa_groth16_vk_bytes",
               "pa_groth16_vk_input_sum_workspace_bytes", "pa_groth16_verify_workspace_bytes",
-              "pa_g1_multiexp_u128_workspace_bytes", "pa_groth16_verify_aggregate_workspace_bytes"):
+              "pa_g1_multiexp_u128_workspace_bytes", "pa_groth16_verify_aggregate_workspace_bytes",
+              "pa_groth16_circuit_rows", "pa_groth16_circuit_cols", "pa_groth16_circuit_n_public",
+              "pa_groth16_circuit_bytes", "pa_groth16_generate_g1_len", "pa_groth16_generate_g2_len",
+              "pa_groth16_generate_workspace_bytes"):
     getattr(_lib, _name).restype = ctypes.c_size_t
 _lib.pa_r1cs_chunk_len.argtypes = []
-for _name in ("pa_r1cs_free", "pa_groth16_pk_free", "pa_groth16_vk_free"):
+for _name in ("pa_r1cs_free", "pa_groth16_pk_free", "pa_groth16_vk_free", "pa_groth16_circuit_free"):
     getattr(_lib, _name).argtypes = [_P]
     getattr(_lib, _name).restype = None
 
@@ -767,3 +782,97 @@ class Groth16Vk(_Handle):
 class FrCsr(ctypes.Structure):
     """pa_fr_csr of the header"""
     _fields_ = [("row_ptr", _P), ("col", _P), ("val", _P)]
+
+
+FR_MODULUS = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+
+
+def trapdoor_rows(trapdoor):
+    """pa_groth16_trapdoor as a (5, 4) uint64 array (tau, alpha, beta, gamma, delta; Montgomery rows), checked as
+    the library checks it: every value below r, gamma and delta not zero"""
+    t = as_rows(trapdoor, W_FR, "trapdoor")
+    if t.shape[0] != 5:
+        raise ValueError("trapdoor must be 5 rows (tau, alpha, beta, gamma, delta), got %d" % t.shape[0])
+    for row, name in zip(t, ("tau", "alpha", "beta", "gamma", "delta")):
+        v = sum(int(x) << (64 * i) for i, x in enumerate(row))
+        if v >= FR_MODULUS:
+            raise ValueError("trapdoor %s is not below r" % name)
+        if v == 0 and name in ("gamma", "delta"):
+            raise ValueError("trapdoor %s must not be zero" % name)
+    return t
+
+
+class Groth16Circuit(_Handle):
+    """A pa_groth16_circuit handle: the transposed matrices of a constraint system on one
+    device, what parameter generation sums over.  `rows` (constraints), `cols` (variables),
+    `n_public` (counting the constant one) and `bytes` (device memory held) are read at
+    creation."""
+
+    WHAT = "Groth16 circuit"
+    FREE = "pa_groth16_circuit_free"
+
+    def __init__(self, handle, rows, cols, n_public, nbytes=0, owns=True):
+        super().__init__(handle, owns)
+        self.rows, self.cols, self.n_public, self.bytes = int(rows), int(cols), int(n_public), int(nbytes)
+
+    @classmethod
+    def _adopt(cls, handle):
+        """take ownership of a handle pa_groth16_circuit_create just returned"""
+        h = ctypes.c_void_p(handle.value)
+        return cls(h, _lib.pa_groth16_circuit_rows(h), _lib.pa_groth16_circuit_cols(h),
+                   _lib.pa_groth16_circuit_n_public(h), _lib.pa_groth16_circuit_bytes(h))
+
+    def check_generate(self, domain):
+        """(handles, log_n) of a generation call after the checks that need no device"""
+        h = self.handle()
+        if not isinstance(domain, FrNttDomain):
+            raise ValueError("domain must come from fr_ntt_domain")
+        hd = domain.handle()
+        if domain.len < self.rows:
+            raise ValueError("the circuit's %d rows exceed the domain's %d points" % (self.rows, domain.len))
+        return (h, hd), domain.log_n
+
+    def g1_len(self, log_n):
+        """records of g1_out: 3 n_vars + 2^log_n + 2"""
+        return 3 * self.cols + (1 << int(log_n)) + 2
+
+    def g2_len(self):
+        """records of g2_out: n_vars + 3"""
+        return self.cols + 3
+
+    def generate_workspace_bytes(self, log_n):
+        """pa_groth16_generate_workspace_bytes; a domain smaller than the circuit's rows is a ValueError"""
+        log_n = int(log_n)
+        if log_n < 0 or log_n > NTT_MAX_LOG_N:
+            raise ValueError("log_n must be 0..%d, got %d" % (NTT_MAX_LOG_N, log_n))
+        if (1 << log_n) < self.rows:
+            raise ValueError("2^%d points do not hold the circuit's %d rows" % (log_n, self.rows))
+        return int(_lib.pa_groth16_generate_workspace_bytes(self.handle(), log_n))
+
+
+class Groth16Params:
+    """What groth16_generate returns: views into the two output arrays (pa_groth16_generate_offsets
+    of the header).  a_query, b_g1_query (n_vars, 13), b_g2_query (n_vars, 25), ic (n_public, 13),
+    l_query (n_vars - n_public, 13), h_query (2^log_n - 1, 13), alpha_g1, beta_g1, delta_g1 (1, 13),
+    beta_g2, gamma_g2, delta_g2 (1, 25); `g1` and `g2` are the whole arrays."""
+
+    def __init__(self, g1, g2, n_vars, n_public, log_n):
+        self.g1, self.g2 = g1, g2
+        self.n_vars, self.n_public, self.log_n = int(n_vars), int(n_public), int(log_n)
+        nv, h0 = self.n_vars, 3 * self.n_vars
+        c0 = h0 + (1 << self.log_n) - 1
+        self.a_query, self.b_g1_query = g1[:nv], g1[nv:2 * nv]
+        self.ic, self.l_query = g1[2 * nv:2 * nv + self.n_public], g1[2 * nv + self.n_public:h0]
+        self.h_query = g1[h0:c0]
+        self.alpha_g1, self.beta_g1, self.delta_g1 = g1[c0:c0 + 1], g1[c0 + 1:c0 + 2], g1[c0 + 2:c0 + 3]
+        self.b_g2_query = g2[:nv]
+        self.beta_g2, self.gamma_g2, self.delta_g2 = g2[nv:nv + 1], g2[nv + 1:nv + 2], g2[nv + 2:nv + 3]
+
+    def pk_args(self):
+        """the arguments of groth16_pk, n_public and log_n included"""
+        return (self.alpha_g1, self.beta_g1, self.delta_g1, self.beta_g2, self.delta_g2, self.a_query,
+                self.b_g1_query, self.b_g2_query, self.l_query, self.h_query, self.n_public, self.log_n)
+
+    def vk_args(self):
+        """the arguments of groth16_vk"""
+        return (self.alpha_g1, self.beta_g2, self.gamma_g2, self.delta_g2, self.ic)

@@ -20,6 +20,7 @@
 #include "launch.h"
 #include "launch_groth16.h"
 #include "launch_groth16_aggregate.h"
+#include "launch_groth16_setup.h"
 #include "launch_groth16_verify.h"
 #include "launch_msm.h"
 
@@ -2037,20 +2038,9 @@ int r1cs_csr_check(const pa_fr_csr* m, size_t n_rows, size_t n_cols) {
     return PA_OK;
 }
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-}  // namespace
 
-int pa_r1cs_create(const pa_fr_csr* a, const pa_fr_csr* b, const pa_fr_csr* c, size_t n_rows, size_t n_cols,
-                   pa_r1cs** out) {
-    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
-    *out = nullptr;
-    if (n_rows > ((size_t)1 << pa::kNttMaxLogN))
-        return fail(PA_ERR_INVALID_ARGUMENT, "R1CS systems support n_rows <= 2^28");
-    const pa_fr_csr* ms[3] = {a, b, c};
-    pa::R1csCsr csr[3];
-    for (int i = 0; i < 3; i++) {
-        if (int rc = r1cs_csr_check(ms[i], n_rows, n_cols)) return rc;
-        csr[i] = {ms[i]->row_ptr, ms[i]->col, (const uint64_t*)ms[i]->val};
-    }
+// the chunked image of three validated CSR matrices of n_rows x n_cols on the current device, copied and waited for
+int r1cs_image_create(const pa::R1csCsr csr[3], size_t n_rows, size_t n_cols, pa_r1cs** out) {
     pa::R1csImage img;
     pa::r1cs_build(csr, n_rows, img);
     const pa::R1csDevLayout lay = pa::r1cs_dev_layout(img);
@@ -2079,6 +2069,22 @@ int pa_r1cs_create(const pa_fr_csr* a, const pa_fr_csr* b, const pa_fr_csr* c, s
     r->d = pa::R1csDev{r->image, lay, img.slabs, n_rows, n_cols, img.n_partial, img.n_fold};
     *out = r;
     return PA_OK;
+}
+}  // namespace
+
+int pa_r1cs_create(const pa_fr_csr* a, const pa_fr_csr* b, const pa_fr_csr* c, size_t n_rows, size_t n_cols,
+                   pa_r1cs** out) {
+    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    *out = nullptr;
+    if (n_rows > ((size_t)1 << pa::kNttMaxLogN))
+        return fail(PA_ERR_INVALID_ARGUMENT, "R1CS systems support n_rows <= 2^28");
+    const pa_fr_csr* ms[3] = {a, b, c};
+    pa::R1csCsr csr[3];
+    for (int i = 0; i < 3; i++) {
+        if (int rc = r1cs_csr_check(ms[i], n_rows, n_cols)) return rc;
+        csr[i] = {ms[i]->row_ptr, ms[i]->col, (const uint64_t*)ms[i]->val};
+    }
+    return r1cs_image_create(csr, n_rows, n_cols, out);
 }
 void pa_r1cs_free(pa_r1cs* r) {
     if (!r) return;
@@ -2347,6 +2353,307 @@ int pa_groth16_prove(const pa_groth16_pk* pk, const pa_r1cs* r1cs, const pa_fr_n
         return rc;
     PA_TRY(call_sync(), "kernel execution");
     return download(proofs, dout, k * sizeof(pa_groth16_proof));
+}
+
+// ---- Groth16 parameter generation: trapdoor -> proving and verifying key (kernels_groth16_setup.hip) ----
+// The circuit object is the pa_r1cs image of the transposed matrices: rows = variables, columns = constraints.
+struct pa_groth16_circuit {
+    pa_r1cs* t = nullptr;
+    size_t n_rows = 0, n_cols = 0, n_public = 0;
+};
+
+int pa_groth16_circuit_create(const pa_fr_csr* a, const pa_fr_csr* b, const pa_fr_csr* c, size_t n_rows, size_t n_cols,
+                              size_t n_public, pa_groth16_circuit** out) {
+    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    *out = nullptr;
+    if (n_rows > ((size_t)1 << pa::kNttMaxLogN))
+        return fail(PA_ERR_INVALID_ARGUMENT, "R1CS systems support n_rows <= 2^28");
+    if (n_cols > ((size_t)1 << pa::kNttMaxLogN))
+        return fail(PA_ERR_INVALID_ARGUMENT, "Groth16 circuits support n_cols <= 2^28");
+    if (n_public > n_cols) return fail(PA_ERR_INVALID_ARGUMENT, "n_public exceeds n_cols");
+    const pa_fr_csr* ms[3] = {a, b, c};
+    pa::R1csCsrOwned tr[3];
+    pa::R1csCsr csr[3];
+    for (int i = 0; i < 3; i++) {
+        if (int rc = r1cs_csr_check(ms[i], n_rows, n_cols)) return rc;
+        pa::r1cs_transpose({ms[i]->row_ptr, ms[i]->col, (const uint64_t*)ms[i]->val}, n_rows, n_cols, tr[i]);
+        csr[i] = {tr[i].row_ptr.data(), tr[i].col.data(), tr[i].val.data()};
+    }
+    pa_r1cs* t = nullptr;
+    if (int rc = r1cs_image_create(csr, n_cols, n_rows, &t)) return rc;
+    pa_groth16_circuit* ci = new pa_groth16_circuit;
+    ci->t = t;
+    ci->n_rows = n_rows;
+    ci->n_cols = n_cols;
+    ci->n_public = n_public;
+    *out = ci;
+    return PA_OK;
+}
+void pa_groth16_circuit_free(pa_groth16_circuit* ci) {
+    if (!ci) return;
+    pa_r1cs_free(ci->t);
+    delete ci;
+}
+size_t pa_groth16_circuit_rows(const pa_groth16_circuit* ci) { return ci ? ci->n_rows : 0; }
+size_t pa_groth16_circuit_cols(const pa_groth16_circuit* ci) { return ci ? ci->n_cols : 0; }
+size_t pa_groth16_circuit_n_public(const pa_groth16_circuit* ci) { return ci ? ci->n_public : 0; }
+size_t pa_groth16_circuit_bytes(const pa_groth16_circuit* ci) { return ci ? pa_r1cs_bytes(ci->t) : 0; }
+size_t pa_groth16_generate_g1_len(const pa_groth16_circuit* ci, unsigned log_n) {
+    return ci && log_n <= pa::kNttMaxLogN ? 3 * ci->n_cols + ((size_t)1 << log_n) + 2 : 0;
+}
+size_t pa_groth16_generate_g2_len(const pa_groth16_circuit* ci) { return ci ? ci->n_cols + 3 : 0; }
+
+namespace {
+// Host Fr for the handful of trapdoor constants of a call: Montgomery rows of 4 x u64 below r (fr.rs:438-572).
+const uint64_t kFrOne[4] = {0x00000001fffffffeull, 0x5884b7fa00034802ull, 0x998c4fefecbc4ff5ull,
+                            0x1824b159acc5056full};
+void fr_host_mul(uint64_t* out, const uint64_t* a, const uint64_t* b) {
+    typedef unsigned __int128 u128;
+    const uint64_t inv = 0xfffffffeffffffffull;   // -r^-1 mod 2^64 (fr.rs:37)
+    uint64_t t[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; i++) {
+        u128 c = 0;
+        for (int j = 0; j < 4; j++) {
+            c += (u128)a[j] * b[i] + t[j];
+            t[j] = (uint64_t)c;
+            c >>= 64;
+        }
+        c += t[4];
+        t[4] = (uint64_t)c;
+        t[5] = (uint64_t)(c >> 64);
+        const uint64_t m = t[0] * inv;
+        c = ((u128)m * kFrModulus[0] + t[0]) >> 64;
+        for (int j = 1; j < 4; j++) {
+            c += (u128)m * kFrModulus[j] + t[j];
+            t[j - 1] = (uint64_t)c;
+            c >>= 64;
+        }
+        c += t[4];
+        t[3] = (uint64_t)c;
+        t[4] = t[5] + (uint64_t)(c >> 64);
+    }
+    // below 2 r < 2^256: t[4] is zero
+    if (!fr_below_r(t)) {
+        u128 br = 0;
+        for (int j = 0; j < 4; j++) {
+            const u128 d = (u128)t[j] - kFrModulus[j] - (uint64_t)br;
+            t[j] = (uint64_t)d;
+            br = (d >> 64) & 1;
+        }
+    }
+    memcpy(out, t, 32);
+}
+void fr_host_sub_one(uint64_t* out, const uint64_t* a) {   // a - 1
+    typedef unsigned __int128 u128;
+    uint64_t t[4];
+    u128 br = 0;
+    for (int j = 0; j < 4; j++) {
+        const u128 d = (u128)a[j] - kFrOne[j] - (uint64_t)br;
+        t[j] = (uint64_t)d;
+        br = (d >> 64) & 1;
+    }
+    if (br) {
+        u128 c = 0;
+        for (int j = 0; j < 4; j++) {
+            c += (u128)t[j] + kFrModulus[j];
+            t[j] = (uint64_t)c;
+            c >>= 64;
+        }
+    }
+    memcpy(out, t, 32);
+}
+void fr_host_inv(uint64_t* out, const uint64_t* a) {   // a^(r - 2)
+    const uint64_t e[4] = {0xfffffffeffffffffull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull};
+    uint64_t acc[4];
+    memcpy(acc, kFrOne, 32);
+    for (int w = 3; w >= 0; w--)
+        for (int bit = 63; bit >= 0; bit--) {
+            fr_host_mul(acc, acc, acc);
+            if ((e[w] >> bit) & 1) fr_host_mul(acc, acc, a);
+        }
+    memcpy(out, acc, 32);
+}
+bool fr_host_is_zero(const uint64_t* a) { return !(a[0] | a[1] | a[2] | a[3]); }
+
+// the call's workspace: byte offsets, every region a multiple of 256
+struct GenLayout {
+    size_t pow, lag, uvw, partial, ntt, s1, s2, base1, base2, jac1, jac2, tab1, cws1, tab2, cws2, fr_bytes, bytes;
+};
+GenLayout gen_layout(const pa_groth16_circuit* ci, unsigned log_n) {
+    GenLayout g{};
+    const size_t n = (size_t)1 << log_n, nv = ci->n_cols, n1 = 3 * nv + n + 2, n2 = nv + 3;
+    size_t o = 0;
+    g.pow = o;      o = align256(o + n * sizeof(pa_fr));
+    g.lag = o;      o = align256(o + n * sizeof(pa_fr));
+    g.uvw = o;      o = align256(o + 3 * nv * sizeof(pa_fr));
+    g.partial = o;  o = align256(o + pa_r1cs_eval_workspace_bytes(ci->t, 1));
+    g.ntt = o;      o = align256(o + n * sizeof(pa_fr));   // a transform of several passes, whatever the tile log
+    g.fr_bytes = o;   // what the scalars entries use
+    g.s1 = o;       o = align256(o + n1 * sizeof(pa_fr_repr));
+    g.s2 = o;       o = align256(o + n2 * sizeof(pa_fr_repr));
+    g.base1 = o;    o = align256(o + sizeof(pa_g1));
+    g.base2 = o;    o = align256(o + sizeof(pa_g2));
+    g.jac1 = o;     o = align256(o + n1 * sizeof(pa_g1));
+    g.jac2 = o;     o = align256(o + n2 * sizeof(pa_g2));
+    g.tab1 = o;     o = align256(o + 8 * pa::g1_comb_table_words());
+    g.cws1 = o;     o = align256(o + 8 * pa::g1_comb_workspace_words());
+    g.tab2 = o;     o = align256(o + 8 * pa::g2_comb_table_words());
+    g.cws2 = o;     o = align256(o + 8 * pa::g2_comb_workspace_words());
+    g.bytes = o;
+    return g;
+}
+
+// what every generation entry refuses before touching memory; fills the kernels' constants
+int gen_check(const pa_groth16_circuit* ci, const pa_fr_ntt_domain* d, const pa_groth16_trapdoor* td,
+              pa::Groth16SetupConsts* k) {
+    if (!td) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    // the trapdoor first: it is host memory and needs no object to be judged
+    const pa_fr* vals[5] = {&td->tau, &td->alpha, &td->beta, &td->gamma, &td->delta};
+    for (const pa_fr* v : vals)
+        if (!fr_below_r(v->l)) return fail(PA_ERR_INVALID_ARGUMENT, "trapdoor value >= r");
+    if (fr_host_is_zero(td->gamma.l) || fr_host_is_zero(td->delta.l))
+        return fail(PA_ERR_INVALID_ARGUMENT, "gamma and delta must not be zero");
+    if (!ci || !d) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    const unsigned log_n = d->layout.log_n;
+    if (((size_t)1 << log_n) < ci->n_rows)
+        return fail(PA_ERR_INVALID_ARGUMENT, "2^log_n is smaller than the circuit's rows");
+    if (ci->t->dev != d->dev)
+        return fail(PA_ERR_INVALID_ARGUMENT, "the circuit and the NTT domain are on different devices");
+    uint64_t p[4], tau_n[4];
+    memcpy(p, td->tau.l, 32);
+    for (unsigned b = 0; b <= 28; b++) {   // p = tau^(2^b)
+        if (b == log_n) memcpy(tau_n, p, 32);
+        if (b < 28) memcpy(k->tau_pow2[b], p, 32);
+        fr_host_mul(p, p, p);
+    }
+    memcpy(k->alpha, td->alpha.l, 32);
+    memcpy(k->beta, td->beta.l, 32);
+    memcpy(k->gamma, td->gamma.l, 32);
+    memcpy(k->delta, td->delta.l, 32);
+    fr_host_inv(k->gamma_inv, td->gamma.l);
+    fr_host_inv(k->delta_inv, td->delta.l);
+    fr_host_sub_one(p, tau_n);
+    fr_host_mul(k->h_scale, p, k->delta_inv);
+    return PA_OK;
+}
+
+// powers, L, u v w and the scalar vectors on `stream`: g1 rows as Montgomery (g2 null) or both as FrRepr
+int gen_scalars(const pa_groth16_circuit* ci, const pa_fr_ntt_domain* d, const pa::Groth16SetupConsts& k,
+                const GenLayout& g, uint8_t* ws, bool montgomery, uint64_t* s1, uint64_t* s2, void* stream) {
+    const unsigned log_n = d->layout.log_n;
+    const size_t n = (size_t)1 << log_n, nv = ci->n_cols;
+    hipStream_t s = (hipStream_t)stream;
+    pa_fr* pow = reinterpret_cast<pa_fr*>(ws + g.pow);
+    pa_fr* lag = reinterpret_cast<pa_fr*>(ws + g.lag);
+    uint64_t* u = reinterpret_cast<uint64_t*>(ws + g.uvw);
+    uint64_t *v = u + 4 * nv, *w = v + 4 * nv;
+    PA_TRY(pa::launch_groth16_setup_powers(k, log_n, (uint64_t*)pow, s), "kernel launch");
+    if (int rc = pa_fr_ntt_device(d, PA_NTT_INVERSE, pow, lag, 1, ws + g.ntt, n * sizeof(pa_fr), stream)) return rc;
+    PA_TRY(pa::launch_r1cs_eval(ci->t->d, (const uint64_t*)lag, 1, nv, u, v, w,
+                                ci->t->d.n_partial ? ws + g.partial : nullptr, s),
+           "kernel launch");
+    PA_TRY(pa::launch_groth16_setup_scalars(k, u, v, w, (const uint64_t*)pow, nv, ci->n_public, n, montgomery, s1, s2,
+                                            s),
+           "kernel launch");
+    return PA_OK;
+}
+int gen_stream_check(const pa_groth16_circuit* ci, void* stream) {
+    int dev = 0;
+    PA_TRY(hipStreamGetDevice((hipStream_t)stream, &dev), "stream device");
+    if (dev != ci->t->dev) return fail(PA_ERR_INVALID_ARGUMENT, "stream is on another device than the circuit");
+    return PA_OK;
+}
+}  // namespace
+
+size_t pa_groth16_generate_workspace_bytes(const pa_groth16_circuit* ci, unsigned log_n) {
+    if (!ci || log_n > pa::kNttMaxLogN || ((size_t)1 << log_n) < ci->n_rows) return 0;
+    return gen_layout(ci, log_n).bytes;
+}
+
+int pa_groth16_generate_scalars_device(const pa_groth16_circuit* ci, const pa_fr_ntt_domain* d,
+                                       const pa_groth16_trapdoor* td, pa_fr* out, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    pa::Groth16SetupConsts k;
+    if (int rc = gen_check(ci, d, td, &k)) return rc;
+    if (!out || !workspace) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    const GenLayout g = gen_layout(ci, d->layout.log_n);
+    if (workspace_bytes < g.bytes)
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_groth16_generate_workspace_bytes");
+    if (int rc = gen_stream_check(ci, stream)) return rc;
+    return gen_scalars(ci, d, k, g, static_cast<uint8_t*>(workspace), true, (uint64_t*)out, nullptr, stream);
+}
+
+int pa_groth16_generate_device(const pa_groth16_circuit* ci, const pa_fr_ntt_domain* d, const pa_g1_affine* g1,
+                               const pa_g2_affine* g2, const pa_groth16_trapdoor* td, pa_g1_affine* g1_out,
+                               pa_g2_affine* g2_out, void* workspace, size_t workspace_bytes, void* stream) {
+    pa::Groth16SetupConsts k;
+    if (int rc = gen_check(ci, d, td, &k)) return rc;
+    if (!g1 || !g2 || !g1_out || !g2_out || !workspace) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    const unsigned log_n = d->layout.log_n;
+    const GenLayout g = gen_layout(ci, log_n);
+    if (workspace_bytes < g.bytes)
+        return fail(PA_ERR_INVALID_ARGUMENT, "workspace smaller than pa_groth16_generate_workspace_bytes");
+    if (int rc = gen_stream_check(ci, stream)) return rc;
+    const size_t n1 = pa_groth16_generate_g1_len(ci, log_n), n2 = pa_groth16_generate_g2_len(ci);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    hipStream_t s = (hipStream_t)stream;
+    uint64_t *s1 = (uint64_t*)(ws + g.s1), *s2 = (uint64_t*)(ws + g.s2);
+    pa_g1 *base1 = (pa_g1*)(ws + g.base1), *jac1 = (pa_g1*)(ws + g.jac1);
+    pa_g2 *base2 = (pa_g2*)(ws + g.base2), *jac2 = (pa_g2*)(ws + g.jac2);
+    int rc;
+    if ((rc = gen_scalars(ci, d, k, g, ws, false, s1, s2, stream))) return rc;
+    PA_TRY(pa::launch_group_op(1, pa::GROUP_FROM_AFFINE, (const uint64_t*)g1, nullptr, (uint64_t*)base1, 1, s),
+           "kernel launch");
+    PA_TRY(pa::launch_group_op(2, pa::GROUP_FROM_AFFINE, (const uint64_t*)g2, nullptr, (uint64_t*)base2, 1, s),
+           "kernel launch");
+    if ((rc = pa_g1_wnaf_fixed_base_device(base1, (const pa_fr_repr*)s1, jac1, n1, (uint64_t*)(ws + g.tab1),
+                                           (uint64_t*)(ws + g.cws1), stream)))
+        return rc;
+    if ((rc = pa_g2_wnaf_fixed_base_device(base2, (const pa_fr_repr*)s2, jac2, n2, (uint64_t*)(ws + g.tab2),
+                                           (uint64_t*)(ws + g.cws2), stream)))
+        return rc;
+    PA_TRY(pa::launch_g1_batch_normalize((uint64_t*)jac1, n1, s), "kernel launch");
+    PA_TRY(pa::launch_groth16_setup_pack(1, (const uint64_t*)jac1, (uint64_t*)g1_out, n1, s), "kernel launch");
+    PA_TRY(pa::launch_g2_batch_normalize((uint64_t*)jac2, n2, s), "kernel launch");
+    PA_TRY(pa::launch_groth16_setup_pack(2, (const uint64_t*)jac2, (uint64_t*)g2_out, n2, s), "kernel launch");
+    return PA_OK;
+}
+
+int pa_groth16_generate_scalars(const pa_groth16_circuit* ci, const pa_fr_ntt_domain* d, const pa_groth16_trapdoor* td,
+                                pa_fr* out) {
+    pa::Groth16SetupConsts k;
+    if (int rc = gen_check(ci, d, td, &k)) return rc;
+    if (!out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    const size_t n1 = pa_groth16_generate_g1_len(ci, d->layout.log_n);
+    const size_t ws = gen_layout(ci, d->layout.log_n).bytes;
+    DevBuf dout, dws;
+    PA_TRY(dout.alloc(n1 * sizeof(pa_fr)), "device scratch");
+    PA_TRY(dws.alloc(ws), "device scratch");
+    if (int rc = pa_groth16_generate_scalars_device(ci, d, td, dout.as<pa_fr>(), dws.p, ws, call_stream())) return rc;
+    PA_TRY(call_sync(), "kernel execution");
+    return download(out, dout, n1 * sizeof(pa_fr));
+}
+
+int pa_groth16_generate(const pa_groth16_circuit* ci, const pa_fr_ntt_domain* d, const pa_g1_affine* g1,
+                        const pa_g2_affine* g2, const pa_groth16_trapdoor* td, pa_g1_affine* g1_out,
+                        pa_g2_affine* g2_out) {
+    pa::Groth16SetupConsts k;
+    if (int rc = gen_check(ci, d, td, &k)) return rc;
+    if (!g1 || !g2 || !g1_out || !g2_out) return fail(PA_ERR_INVALID_ARGUMENT, "null pointer");
+    const size_t n1 = pa_groth16_generate_g1_len(ci, d->layout.log_n), n2 = pa_groth16_generate_g2_len(ci);
+    const size_t ws = gen_layout(ci, d->layout.log_n).bytes;
+    DevBuf dg1, dg2, do1, do2, dws;
+    int rc;
+    if ((rc = upload(dg1, g1, sizeof(pa_g1_affine))) || (rc = upload(dg2, g2, sizeof(pa_g2_affine)))) return rc;
+    PA_TRY(do1.alloc(n1 * sizeof(pa_g1_affine)), "device scratch");
+    PA_TRY(do2.alloc(n2 * sizeof(pa_g2_affine)), "device scratch");
+    PA_TRY(dws.alloc(ws), "device scratch");
+    if ((rc = pa_groth16_generate_device(ci, d, dg1.as<pa_g1_affine>(), dg2.as<pa_g2_affine>(), td,
+                                         do1.as<pa_g1_affine>(), do2.as<pa_g2_affine>(), dws.p, ws, call_stream())))
+        return rc;
+    PA_TRY(call_sync(), "kernel execution");
+    if ((rc = download(g1_out, do1, n1 * sizeof(pa_g1_affine)))) return rc;
+    return download(g2_out, do2, n2 * sizeof(pa_g2_affine));
 }
 
 // ---- Groth16 verifier: the prepared verifying key, and proofs -> valid (kernels_groth16_verify.hip) ----

@@ -211,8 +211,12 @@ R1csDevLayout r1cs_dev_layout(const R1csImage& img) {
 
 hipError_t launch_r1cs_eval(const R1csDev& r, const uint64_t* witness, size_t k, unsigned log_n, uint64_t* a,
                             uint64_t* b, uint64_t* c, void* workspace, hipStream_t stream) {
+    return launch_r1cs_eval(r, witness, k, (size_t)1 << log_n, a, b, c, workspace, stream);
+}
+
+hipError_t launch_r1cs_eval(const R1csDev& r, const uint64_t* witness, size_t k, size_t n, uint64_t* a, uint64_t* b,
+                            uint64_t* c, void* workspace, hipStream_t stream) {
     if (k == 0) return hipSuccess;
-    const size_t n = (size_t)1 << log_n;
     const uint8_t* base = static_cast<const uint8_t*>(r.image);
     const unsigned slab_blocks = (unsigned)((r.slabs.first[3] + 3) / 4);
     const size_t pad_blocks = (3 * (n - r.n_rows) + 255) / 256;

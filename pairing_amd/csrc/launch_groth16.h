@@ -50,6 +50,9 @@ R1csDevLayout r1cs_dev_layout(const R1csImage& img);
 // a, b, c: k polynomials of 2^log_n rows; workspace: k * n_partial rows of 32 bytes
 hipError_t launch_r1cs_eval(const R1csDev& r, const uint64_t* witness, size_t k, unsigned log_n, uint64_t* a,
                             uint64_t* b, uint64_t* c, void* workspace, hipStream_t stream);
+// the same over outputs of n >= n_rows rows each, n any count (n = n_rows: nothing is padded)
+hipError_t launch_r1cs_eval(const R1csDev& r, const uint64_t* witness, size_t k, size_t n, uint64_t* a, uint64_t* b,
+                            uint64_t* c, void* workspace, hipStream_t stream);
 
 // ---- proof assembly (kernels_groth16.hip) ----
 // consts: alpha_g1, beta_g1, delta_g1 (13 u64 affine records each), then beta_g2, delta_g2 (25 u64 each).

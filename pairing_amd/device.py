@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, W_PROOF, FrNttDomain, G1MsmBases, G2MsmBases, Groth16Pk, Groth16Vk, R1cs, _lib, call, csr_offsets, msm_bases, msm_scalars, ntt_mode
+from ._native import W_FQ, W_FQ12, W_G1, W_G1A, W_G2, W_G2A, W_G2P, W_PROOF, FrNttDomain, G1MsmBases, G2MsmBases, Groth16Circuit, Groth16Pk, Groth16Vk, R1cs, _lib, call, csr_offsets, msm_bases, msm_scalars, ntt_mode, trapdoor_rows
 
 
 def _stream_ptr(stream):
@@ -419,6 +419,56 @@ def groth16_prove(pk, system, domain, witness, r, s, out, workspace, stream=None
     args = (_dptr(witness, 4, "witness"), _dptr(r, 4, "r"), _dptr(s, 4, "s"))
     call("pa_groth16_prove_device", h, hr, hd, *args, k, _dptr(out, W_PROOF, "out"),
          ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
+
+
+def groth16_generate_workspace(circuit, log_n, device):
+    """A device workspace sized for groth16_generate and groth16_generate_scalars over a domain
+    of 2^log_n points (pa_groth16_generate_workspace_bytes)."""
+    if not isinstance(circuit, Groth16Circuit):
+        raise ValueError("circuit must come from groth16_circuit")
+    return torch.empty(circuit.generate_workspace_bytes(log_n), dtype=torch.uint8, device=device)
+
+
+def _generate_args(circuit, domain, trapdoor, workspace):
+    """(handles, log_n, trapdoor rows, workspace pointer, bytes) after the checks that need no device"""
+    if not isinstance(circuit, Groth16Circuit):
+        raise ValueError("circuit must come from groth16_circuit")
+    (h, hd), log_n = circuit.check_generate(domain)
+    if getattr(trapdoor, "is_cuda", False):
+        raise ValueError("trapdoor must be host memory (a numpy array or a CPU tensor)")
+    t = trapdoor_rows(trapdoor.numpy().view("uint64") if isinstance(trapdoor, torch.Tensor) else trapdoor)
+    need = circuit.generate_workspace_bytes(log_n)
+    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.dtype != torch.uint8 \
+            or workspace.numel() < need:
+        raise ValueError("workspace must be a contiguous uint8 CUDA tensor of >= %d bytes" % need)
+    return (h, hd), log_n, t, ctypes.c_void_p(workspace.data_ptr()), workspace.numel()
+
+
+def groth16_generate(circuit, domain, g1, g2, trapdoor, g1_out, g2_out, workspace, stream=None):
+    """bellman's generate_parameters for the given trapdoor into g1_out ((rows, 13) int64, the
+    first 3 n_vars + 2^log_n + 2 rows: a_query | b_g1_query | ic | l_query | h_query | alpha_g1,
+    beta_g1, delta_g1) and g2_out ((rows, 25), the first n_vars + 3: b_g2_query | beta_g2,
+    gamma_g2, delta_g2), affine records.  g1 (1, 13) and g2 (1, 25) are the base points in HBM;
+    trapdoor is host memory, (5, 4) Montgomery rows tau, alpha, beta, gamma, delta; workspace
+    from groth16_generate_workspace.  Everything is enqueued on the stream; nothing is
+    allocated, synchronized or read back."""
+    (h, hd), log_n, t, ws, ws_bytes = _generate_args(circuit, domain, trapdoor, workspace)
+    _rows(g1, 1, "g1")
+    _rows(g2, 1, "g2")
+    _rows(g1_out, circuit.g1_len(log_n), "g1_out")
+    _rows(g2_out, circuit.g2_len(), "g2_out")
+    call("pa_groth16_generate_device", h, hd, _dptr(g1, W_G1A, "g1"), _dptr(g2, W_G2A, "g2"),
+         ctypes.c_void_p(t.ctypes.data), _dptr(g1_out, W_G1A, "g1_out"), _dptr(g2_out, W_G2A, "g2_out"), ws, ws_bytes,
+         _stream_ptr(stream))
+
+
+def groth16_generate_scalars(circuit, domain, trapdoor, out, workspace, stream=None):
+    """The discrete logarithms of groth16_generate's G1 array, in its order, into the first
+    3 n_vars + 2^log_n + 2 rows of `out` ((rows, 4) int64 Montgomery Fr rows)."""
+    (h, hd), log_n, t, ws, ws_bytes = _generate_args(circuit, domain, trapdoor, workspace)
+    _rows(out, circuit.g1_len(log_n), "out")
+    call("pa_groth16_generate_scalars_device", h, hd, ctypes.c_void_p(t.ctypes.data), _dptr(out, 4, "out"), ws,
+         ws_bytes, _stream_ptr(stream))
 
 
 def groth16_verify_workspace(vk, k, device):
