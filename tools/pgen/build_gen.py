@@ -143,6 +143,25 @@ FILES = {"small": "pa_gen_small.hsaco", "cyc": "pa_gen_cyc.hsaco", "ml": "pa_gen
          "tdec": "test/pa_gen_tdec.hsaco", "tunit": "test/pa_gen_tunit.hsaco", "tdec2": "test/pa_gen_tdec2.hsaco"}
 
 
+def _ml_step(which, lanes, pairing_only):
+    return lambda: __import__("unit_progs").ml_step_prog(which, lanes=lanes, pairing_only=pairing_only)
+
+
+# test-only kernels of the Miller loop's pieces (unit_progs.ml_step_prog, tests/test_ml_steps_gpu.py):
+# the lane-pair objects built as ml2 / ml2p are (two_pass, xi by swap), the one-lane loop as ml1p is
+ML_STEP_OBJS = {"tml2_%s%s" % (w, "h" if h else ""): (w, 2, h)
+                for w, hs in (("dbl", (False, True)), ("add", (False, True)), ("ell", (False,)), ("sqr12", (False,)),
+                              ("mul12", (False,)), ("iter", (False, True))) for h in hs}
+ML_STEP_OBJS["tml1_iterh"] = ("iter", 1, True)
+for _key, (_w, _lanes, _h) in ML_STEP_OBJS.items():
+    if _lanes == 2:
+        PROGRAMS[_key] = _mk(__import__("tower2").two_pass(_ml_step(_w, 2, _h), xi_dpp=False), kcfg.FinalExpCfg2,
+                             "pa_gen_" + _key)
+    else:
+        PROGRAMS[_key] = _mk(_ml_step(_w, 1, _h), kcfg.FinalExpCfg, "pa_gen_" + _key)
+    FILES[_key] = "test/pa_gen_%s.hsaco" % _key
+
+
 def build(which, outdir):
     t = time.time()
     f = PROGRAMS[which]

@@ -135,57 +135,80 @@ ML_HOMES = {"px": "L", "py": "L", "qx0": "M", "qx1": "M", "qy0": "M", "qy1": "M"
 ML2_HOMES = {"f": "LLLLLLLLLLMM", "px": "M", "rx0": "M", "ry0": "M", "rz0": "M"}
 
 
+def ml_homes(lanes, homes=None):
+    """the Miller loop's variable homes: ML_HOMES, over lane pairs with
+    ML2_HOMES on top, then the caller's own"""
+    base = dict(ML_HOMES, **ML2_HOMES) if lanes == 2 and os.environ.get("PGEN_ML2_HOMES", "1") == "1" else ML_HOMES
+    return dict(base, **(homes or {}))
+
+
+def g2_steps(pairing_only):
+    """(doubling step, addition step) of the reference / of the pairing-only kernels"""
+    return (doubling_step_h, addition_step_h) if pairing_only else (doubling_step, addition_step)
+
+
+def ml_declare(p, V, homes):
+    """declare the Miller loop's state variables in their homes: P (px, py;
+    lane pairs pack both into px), the affine Q, the G2 point R and f"""
+    for n in ("px", "py", "qx0", "qx1", "qy0", "qy1", "rx0", "rx1", "ry0", "ry1", "rz0", "rz1"):
+        p.var(n, 1, homes.get(n))
+    V.declare12("f", homes.get("f"))
+
+
+def line(p, T, V, steps, step):
+    """one line of the Miller loop on the state variables (ml_declare): the
+    G2 step `step` ("dbl" / "add") of steps = (doubling, addition) on R (and
+    Q), then f times the line at P (ell).  The product loops
+    (miller_loop_prog) and their unit program (unit_progs.ml_step_prog "iter")
+    share it."""
+    lanes = p.lanes
+    dbl, add = steps
+    r = tuple(V.get2(n) for n in ("rx", "ry", "rz"))
+    if step == "dbl":
+        c, r = dbl(T, r)
+    else:
+        c, r = add(T, r, V.get2("qx"), V.get2("qy"))
+    for n, v in zip(("rx", "ry", "rz"), r):
+        V.set2(n, v)
+    if lanes == 1:
+        px, py = p.get("px"), p.get("py")
+    else:   # replicate P's coordinates from the packed (px | py) slot
+        pk = p.get("px")
+        px, py = p.bcast(pk, 0), p.bcast(pk, 1)
+    V.set12("f", ell(T, V.get12("f"), c, px, py))
+
+
 def miller_loop_prog(homes=None, lanes=1, lazy=False, pairing_only=False):
     """pairing_only: the G2 steps in homogeneous coordinates with their own
     line scaling (doubling_step_h / addition_step_h): f differs from the
     reference's Miller value by an Fq2 factor, which the final exponentiation
     removes ((q^12 - 1) / r is a multiple of q^2 - 1) -- for e(P, Q) only"""
-    base = dict(ML_HOMES, **ML2_HOMES) if lanes == 2 and os.environ.get("PGEN_ML2_HOMES", "1") == "1" else ML_HOMES
-    homes = dict(base, **(homes or {}))
+    homes = ml_homes(lanes, homes)
     name = ("miller_loop" if lanes == 1 else "miller_loop2") + ("p" if pairing_only else "")
     p = Prog(name, lanes, use_norm=_norm(lanes))
-    dbl, add = (doubling_step_h, addition_step_h) if pairing_only else (doubling_step, addition_step)
+    steps = g2_steps(pairing_only)
     T = (TowerLazy(p) if lazy else Tower(p)) if lanes == 1 else Tower2(p)
     V = _Vars(p, lanes)
-    for n in ("px", "py"):
-        p.var(n, 1, homes.get(n))
+    ml_declare(p, V, homes)
     if lanes == 1:
         p.set("px", p.load(0))
         p.set("py", p.load(1))
     else:
         p.set("px", p.load(0, 1))    # lane 0: px, lane 1: py
-    for n in ("qx0", "qx1", "qy0", "qy1", "rx0", "rx1", "ry0", "ry1", "rz0", "rz1"):
-        p.var(n, 1, homes.get(n))
     V.set2("qx", (p.load(2), p.load(3)) if lanes == 1 else p.load(2, 3))
     V.set2("qy", (p.load(4), p.load(5)) if lanes == 1 else p.load(4, 5))
-    V.declare12("f", homes.get("f"))
     zero = T.const2((0, 0))
     V.set2("rx", V.get2("qx"))
     V.set2("ry", V.get2("qy"))
     V.set2("rz", T.one2())
     V.set12("f", ((T.one2(), zero, zero), (zero, zero, zero)))
 
-    def line(step):
-        r = tuple(V.get2(n) for n in ("rx", "ry", "rz"))
-        if step == "dbl":
-            c, r = dbl(T, r)
-        else:
-            c, r = add(T, r, V.get2("qx"), V.get2("qy"))
-        for n, v in zip(("rx", "ry", "rz"), r):
-            V.set2(n, v)
-        if lanes == 1:
-            px, py = p.get("px"), p.get("py")
-        else:   # replicate P's coordinates from the packed (px | py) slot
-            pk = p.get("px")
-            px, py = p.bcast(pk, 0), p.bcast(pk, 1)
-        V.set12("f", ell(T, V.get12("f"), c, px, py))
-
     with p.loop(62) as L:
-        line("dbl")
+        line(p, T, V, steps, "dbl")
         with p.if_bit(ML_MASK, L):
-            line("add")
+            line(p, T, V, steps, "add")
         V.set12("f", T.sqr12(V.get12("f")))
-    line("dbl")
+    line(p, T, V, steps, "dbl")
     V.store12(T.conj12(V.get12("f")))
     return p
 
